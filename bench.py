@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py — GP posterior predictions/sec, fp64, C3 (n=4096 train, m=100k test, d=8).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+what takes runs of its own: the untimed steps behind the auxiliary rooflines / per-phase times
+and the CPU baseline with its parity check (``--no-cpu`` leaves the baseline out of a full
+run).  ``--dump-outputs DIR`` writes what the last timed step returned to ``DIR/<name>.npy``
+(workloads c3, c4, c5; the inputs are seeded, so two builds can be compared output for output).
 
 A step is one full pass of the hot path for one GP, from hyperparameters to answers on rank 0:
 ARD-SE Gram (n x n) -> blocked MFMA Cholesky + L^-1 -> cross-covariance / TRMM / mean+variance
@@ -29,9 +35,10 @@ GPs, n = 1024, m = 100k shared test points): rank 0 broadcasts the inputs over R
 setup, the PCs are dealt round-robin to ranks, each step ends with one gather of every
 rank's (mean, var) rows to rank 0 (strong scaling: total work fixed).
 
-rank 0 prints ONE JSON line with the metric, a roofline object for the dominant kernel
-(trmm_pair_kernel, timed live with HIP events on its own stream via gp_profile_*), auxiliary
-rooflines, and a CPU baseline (the numpy fp64 oracle on the host cores, bounded sample).
+rank 0 prints ONE JSON line with the metric and a roofline object for the dominant kernel
+(trmm_pair_kernel, timed live with HIP events on its own stream via gp_profile_*); with
+``--full`` also auxiliary rooflines and a CPU baseline (the numpy fp64 oracle on the host
+cores, bounded sample).
 """
 from __future__ import annotations
 
@@ -86,6 +93,32 @@ def c4_inputs(n: int, m: int, d: int, P: int):
     W = np.stack([np.random.default_rng(100 + j).standard_normal(n) for j in range(P)])
     Xs = np.random.default_rng(2).random((m, d))
     return X, W, beta, Xs, np.ones(P), np.full(P, 1e-6)
+
+
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """``--dump-outputs``: write each tensor of ``arrays`` (what the last timed step returned
+    to its caller) as ``dirname/<name>.npy``, float32 and float64 as they are, anything else as
+    float64.  Past ``DUMP_MAX_BYTES`` in all, every array is cut by the same factor to a fixed
+    sample of its flattened elements (sorted indices drawn from rng(0), the same from run to
+    run for the same shapes), gathered on the device so a large field never goes to the host
+    whole."""
+    os.makedirs(dirname, exist_ok=True)
+    tens = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        tens[name] = t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float64)
+    total = sum(t.numel() * t.element_size() for t in tens.values())
+    frac = min(1.0, DUMP_MAX_BYTES / max(total, 1))
+    rng = np.random.default_rng(0)
+    for name, t in tens.items():
+        if frac < 1.0:
+            k = max(1, int(t.numel() * frac))
+            idx = np.sort(rng.integers(0, t.numel(), size=k))
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_model() -> str:
@@ -247,7 +280,7 @@ def c3_pipelined(args, ctx, X, y, beta, Xs, s, delta, timed):
     def num(v, scale):      # one rank measures nothing (calibrate_split: the split is [m])
         return None if v is None or v != v else v * scale
     return {"elapsed": elapsed, "counts": pp.counts, "t_fact_ms": num(pp.t_fact, 1e3),
-            "t_point_us": num(pp.t_point, 1e6), "check": check}
+            "t_point_us": num(pp.t_point, 1e6), "check": check, "res": state["res"]}
 
 
 def _free_port() -> int:
@@ -331,7 +364,16 @@ def main():
     ap.add_argument("--m-chunk", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=20000,
                     help="test points the CPU baseline predicts per run (median of 3 runs)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the untimed steps behind the "
+                         "auxiliary rooflines / per-phase times, and the CPU baseline with its "
+                         "parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as "
+                         "DIR/<name>.npy (c3, c4, c5; at most 64 MB in all, a fixed seeded "
+                         "sample of larger outputs)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="--full: leave the CPU baseline out")
     ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling leg (N > 1)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing only: every rank on cuda:0 over gloo (host-staged collectives)")
@@ -382,6 +424,8 @@ def main():
                          "60.55 vs 60.67-61.13 ms/step, profiles/r04/r04d_c4_aux_chunks.log), "
                          "or gram -> potrf -> gp_predict")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("fit", "latency"):
+        ap.error(f"--dump-outputs: not available for --workload {args.workload}")
     rc = launch_ranks(args)
     if rc is not None:
         sys.exit(rc)
@@ -454,21 +498,23 @@ def main():
         _capi.call("gp_profile_enable", 64 * (args.steps + 1))
     # the timed region records only the dominant kernel's events (one pair around a step's
     # TRMM launches): the Gram / factorisation / cross-covariance pairs would sit on the
-    # critical path of every step; they are read from two untimed steps after it
+    # critical path of every step; --full reads them from two untimed steps after it
     select = getattr(_capi.lib(), "gp_profile_select", lambda mask: 0)   # (older builds: A/B)
     select(1 << _capi.PROF_TRMM)
     _capi.call("gp_profile_reset")
     elapsed = timed(strong_step, args.steps)
+    last = gathered[0]                  # what the last timed step returned (rank 0)
     prof = {"trmm": read_prof(_capi.PROF_TRMM)}
     select(0xFFFFFFFF)
     aux_steps = 2
-    _capi.call("gp_profile_reset")
-    for _ in range(aux_steps):
-        strong_step()
-    torch.cuda.synchronize()
-    prof.update({k: read_prof(v) for k, v in (("gram", _capi.PROF_GRAM),
-                                              ("potrf", _capi.PROF_POTRF),
-                                              ("cross", _capi.PROF_CROSS))})
+    if args.full:
+        _capi.call("gp_profile_reset")
+        for _ in range(aux_steps):
+            strong_step()
+        torch.cuda.synchronize()
+        prof.update({k: read_prof(v) for k, v in (("gram", _capi.PROF_GRAM),
+                                                  ("potrf", _capi.PROF_POTRF),
+                                                  ("cross", _capi.PROF_CROSS))})
     _capi.call("gp_profile_enable", 0)
 
     weak = None
@@ -487,7 +533,7 @@ def main():
                         "no collective)"}
         del Xwd, ow
 
-    res = None if gathered[0] is None else torch.stack(gathered[0])   # (2, m) on rank 0
+    res = None if last is None else torch.stack(last)   # (2, m) on rank 0
     if fctx is not None:
         fctx.close()
     pipe = None
@@ -519,34 +565,36 @@ def main():
             "flop_per_launch": tr_flops / max(tr_cnt, 1),
             "work_note": "n^2 + 4n flop per prediction (lower-triangular L^-1 K*^T + mean/var), "
                          "rank 0's test points"}
-    g_cnt, g_ms = prof["gram"]
-    g_bytes = (4.0 * n * (n + 1) + 8.0 * n * d) * g_cnt   # lower triangle written + X read
-    p_cnt, p_ms = prof["potrf"]
-    p_flops = 2.0 * n ** 3 / 3.0 * p_cnt
-    c_cnt, c_ms = prof["cross"]
-    npad = kernels.padded_n(n)
-    c_bytes = 8.0 * npad * ml * aux_steps
-    aux = {
-        "gram": {"bound": "hbm", "achieved": round(g_bytes / (g_ms * 1e-3) / 1e9, 1),
-                 "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                 "frac": round(g_bytes / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                 "avg_launch_ms": round(g_ms / max(g_cnt, 1), 4),
-                 "work_note": "4n(n+1) B written (lower triangle) + 8nd B read per launch"},
-        "potrf_inv": {"bound": "mfma", "achieved": round(p_flops / (p_ms * 1e-3) / 1e12, 3),
-                      "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                      "frac": round(p_flops / (p_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 4),
-                      "avg_call_ms": round(p_ms / max(p_cnt, 1), 4),
-                      "work_note": "potrf n^3/3 + triangular inverse n^3/3"},
-        "cross": {"bound": "hbm", "achieved": round(c_bytes / (c_ms * 1e-3) / 1e9, 1),
-                  "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                  "frac": round(c_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                  "ms_per_step": round(c_ms / aux_steps, 4),
-                  "work_note": "8 B written per (padded train row, test point)"},
-        "trmm_ms_per_step": round(tr_ms / K, 4),
-        "note": "gram / potrf_inv / cross timed over two untimed steps after the timed region "
-                "(their event pairs would sit on every step's critical path); the TRMM's over "
-                "the timed region",
-    }
+    aux = None
+    if args.full:
+        g_cnt, g_ms = prof["gram"]
+        g_bytes = (4.0 * n * (n + 1) + 8.0 * n * d) * g_cnt   # lower triangle written + X read
+        p_cnt, p_ms = prof["potrf"]
+        p_flops = 2.0 * n ** 3 / 3.0 * p_cnt
+        c_cnt, c_ms = prof["cross"]
+        npad = kernels.padded_n(n)
+        c_bytes = 8.0 * npad * ml * aux_steps
+        aux = {
+            "gram": {"bound": "hbm", "achieved": round(g_bytes / (g_ms * 1e-3) / 1e9, 1),
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(g_bytes / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                     "avg_launch_ms": round(g_ms / max(g_cnt, 1), 4),
+                     "work_note": "4n(n+1) B written (lower triangle) + 8nd B read per launch"},
+            "potrf_inv": {"bound": "mfma", "achieved": round(p_flops / (p_ms * 1e-3) / 1e12, 3),
+                          "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                          "frac": round(p_flops / (p_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 4),
+                          "avg_call_ms": round(p_ms / max(p_cnt, 1), 4),
+                          "work_note": "potrf n^3/3 + triangular inverse n^3/3"},
+            "cross": {"bound": "hbm", "achieved": round(c_bytes / (c_ms * 1e-3) / 1e9, 1),
+                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                      "frac": round(c_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                      "ms_per_step": round(c_ms / aux_steps, 4),
+                      "work_note": "8 B written per (padded train row, test point)"},
+            "trmm_ms_per_step": round(tr_ms / K, 4),
+            "note": "gram / potrf_inv / cross timed over two untimed steps after the timed region "
+                    "(their event pairs would sit on every step's critical path); the TRMM's over "
+                    "the timed region",
+        }
     line = {
         "metric": METRIC, "value": value, "unit": "predictions/s", "n_gpus": ctx.world,
         "steps": K, "warmup": args.warmup, "ms_per_step": elapsed / K * 1e3,
@@ -591,7 +639,11 @@ def main():
                                       "+ gp_predict_z of the next GP, first")
         line["pipeline"] = {"t_fact_ms": pipe["t_fact_ms"], "t_point_us": pipe["t_point_us"],
                             "check_last_step_vs_direct": pipe["check"]}
-    if ctx.world == 1 and not args.no_cpu:
+    if args.dump_outputs:
+        # the headline path's last timed step: the pipelined schedule's at N > 1
+        shown = res if pipe is None or pipe["res"] is None else pipe["res"]
+        dump_outputs(args.dump_outputs, {"mean": shown[0], "var": shown[1]})
+    if args.full and ctx.world == 1 and not args.no_cpu:
         cb, mu_ref, var_ref = cpu_baseline(X, y, beta, Xs, s, delta, args.cpu_sample,
                                            faithful_batches=args.cpu_faithful_batches)
         k = mu_ref.shape[0]
@@ -712,7 +764,9 @@ def main_c4(args):
         "cpu_baseline": None,
     }
     assert out is not None and out[0].shape == (P, m)
-    if ctx.world == 1 and not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mean": out[0], "var": out[1]})
+    if args.full and ctx.world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline_c4(X, W, beta, Xs, s, delta, out)
     print(json.dumps(line), flush=True)
 
@@ -851,7 +905,7 @@ def main_latency(args):
                               "returns numpy); error = the harness's own host numpy loop"},
         "roofline": None, "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_latency_baseline(data, model, samples, t_test[0:1], sd_y)
     print(json.dumps(line), flush=True)
 
@@ -953,18 +1007,22 @@ def main_c5(args):
     tr_cnt, tr_ms = read_prof(_capi.PROF_TRMM)
     select(0xFFFFFFFF)
     _capi.call("gp_profile_enable", 0)
-    # per-phase device times: events on the pipeline's stream over two untimed steps after the
-    # timed region (event pairs inside it would add their own waits)
-    phase_steps = 2
-    ph = {}
-    for _ in range(phase_steps):
-        pipe.events = []
-        res = pipe.run()
-        torch.cuda.synchronize()
-        evs = pipe.events
-        for (a, ea), (b, eb) in zip(evs[:-1], evs[1:]):
-            ph[b] = ph.get(b, 0.0) + ea.elapsed_time(eb) / phase_steps
-    pipe.events = None
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, {k: res[k] for k in ("mean", "var", "y", "K", "S")})
+    # --full: per-phase device times from events on the pipeline's stream over two untimed
+    # steps after the timed region (event pairs inside it would add their own waits)
+    ph = None
+    if args.full:
+        phase_steps = 2
+        ph = {}
+        for _ in range(phase_steps):
+            pipe.events = []
+            res = pipe.run()
+            torch.cuda.synchronize()
+            evs = pipe.events
+            for (a, ea), (b, eb) in zip(evs[:-1], evs[1:]):
+                ph[b] = ph.get(b, 0.0) + ea.elapsed_time(eb) / phase_steps
+        pipe.events = None
     if ctx.rank != 0:
         pipe.close()
         return
@@ -974,14 +1032,6 @@ def main_c5(args):
     bl = len(gdist.shard_units(S * P, 0, ctx.world))
     tr_flops = float(bl) * m * K * (n * n + 4 * n)
     tr_tfs = tr_flops / (tr_ms * 1e-3) / 1e12 if tr_ms > 0 else 0.0
-    y = res["y"]
-    ny_r = y.shape[-1]
-    svd_bytes = 4.0 * n * ny * 8 + ny * P * 4          # y_std read by the 4 ensemble products
-    svd_s = ph["svd"] * 1e-3
-    fy_s = ph["get_y"] * 1e-3
-    fy_flop = 2.0 * S * m * ny_r * P
-    fy_bytes = S * m * ny_r * y.element_size() + S * m * P * 8 + P * ny_r * 8
-    pr_s = ph["predict"] * 1e-3
     c5_traffic = (None, None)
     tf = os.path.join(ROOT, "profiles", "r06", "pmc_traffic_c5.json")
     tj = json.load(open(tf)) if os.path.exists(tf) else {}
@@ -1011,7 +1061,7 @@ def main_c5(args):
                                    if ctx.distributed else "1 GPU"),
                    "collectives": (f"{ctx.backend} process group of {ctx.world}"
                                    if ctx.distributed else "none (single process)")},
-        "phases_ms": {k: round(v, 4) for k, v in ph.items()},
+        "phases_ms": None,
         "roofline": {"kernel": prediction_kernel(n), "bound": "mfma",
                      "achieved": round(tr_tfs, 3), "peak": FP64_MFMA_PEAK_TFLOPS,
                      "unit": "TFLOP/s", "frac": round(tr_tfs / FP64_MFMA_PEAK_TFLOPS, 4),
@@ -1021,7 +1071,20 @@ def main_c5(args):
                      "flop_per_launch": tr_flops / max(tr_cnt, 1),
                      "work_note": "n^2 + 4n flop per prediction (the fused kernel also "
                                   "produces the cross-covariance: its exp work is not counted)"},
-        "roofline_phases": {
+        "roofline_phases": None,
+        "cpu_baseline": None,
+    }
+    if ph is not None:
+        line["phases_ms"] = {k: round(v, 4) for k, v in ph.items()}
+        y = res["y"]
+        ny_r = y.shape[-1]
+        svd_bytes = 4.0 * n * ny * 8 + ny * P * 4          # y_std read by the 4 ensemble products
+        svd_s = ph["svd"] * 1e-3
+        fy_s = ph["get_y"] * 1e-3
+        fy_flop = 2.0 * S * m * ny_r * P
+        fy_bytes = S * m * ny_r * y.element_size() + S * m * P * 8 + P * ny_r * 8
+        pr_s = ph["predict"] * 1e-3
+        line["roofline_phases"] = {
             "svd": {"bound": "hbm", "achieved": round(svd_bytes / svd_s / 1e9, 1),
                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": round(svd_bytes / svd_s / 1e9 / HBM_PEAK_GBS, 4),
@@ -1048,10 +1111,8 @@ def main_c5(args):
                                    "written per field element (+ w and K read): the fp64 "
                                    "product bounds it (1.63 ms at peak vs 0.5 ms of writes at "
                                    "C5); gp_field"},
-        },
-        "cpu_baseline": None,
-    }
-    if ctx.world == 1 and not args.no_cpu:
+        }
+    if args.full and ctx.world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline_c5(pipe, res, args.c5_cpu_sample)
     pipe.close()
     print(json.dumps(line), flush=True)
@@ -1278,9 +1339,10 @@ def main_fit(args):
                         "value": float(tim[2]) + float(tim[3])}
         sweeps = 100 * 5 + 100 + 512      # burn-in + 5 tuning levels + samples
         pca_s, mcmc_s = float(tim[2]), float(tim[3])
-        roof = fit_roofline(models[-1], mcmc_s, sweeps)
+        # --full: the factorisation's roofline (timed runs of its own) and the CPU baseline
+        roof = fit_roofline(models[-1], mcmc_s, sweeps) if args.full else None
         cpu = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             cpu = cpu_baseline_fit(models[-1], cfg, n, P, sweeps, args.fit_cpu_sweeps,
                                    args.fit_cpu_ny_frac)
     finally:

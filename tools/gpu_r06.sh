@@ -13,11 +13,11 @@ for step in "$@"; do
     t_*) f=${step#t_}; run "$step" 600 $PYT "tests/test_gpu_${f}.py" || exit $? ;;
     gpu) run gpu 1100 $PYT -m gpu tests || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 400 python -u bench.py || exit $? ;;
-    c4) run c4 400 python -u bench.py --workload c4 || exit $? ;;
-    c5) run c5 400 python -u bench.py --workload c5 || exit $? ;;
+    bench) run bench 400 python -u bench.py --full || exit $? ;;
+    c4) run c4 400 python -u bench.py --full --workload c4 || exit $? ;;
+    c5) run c5 400 python -u bench.py --full --workload c5 || exit $? ;;
     c5q) run c5q 300 python -u bench.py --workload c5 --no-cpu --steps 5 --warmup 2 || exit $? ;;
-    fit) run fit 400 python -u bench.py --workload fit || exit $? ;;
+    fit) run fit 400 python -u bench.py --full --workload fit || exit $? ;;
     prof_c5) run prof_c5 400 rocprofv3 --kernel-trace --stats -d gpurun_out/r06_${tag}_prof_c5 -o c5 -- python -u bench.py --workload c5 --no-cpu --steps 5 --warmup 2 || exit $? ;;
     field_ab) run field_ab 300 python -u tools/field_ab.py || exit $? ;;
     c4q) run c4q 300 python -u bench.py --workload c4 --no-cpu --steps 5 --warmup 2 || exit $? ;;
@@ -31,7 +31,7 @@ for step in "$@"; do
     pmc_res) run pmc_res 600 bash tools/pmc_res.sh r06_pmc_res || exit $? ;;
     ab_res2) run ab_res2 1100 bash tools/ab_res2.sh r06_ab_res2_inner "${AB_LIBS:-_ab/libgpfit_narrow.so}" "${AB_MODES:-2 1}" || exit $? ;;
     prof_c3) run prof_c3 400 rocprofv3 --kernel-trace --stats -d gpurun_out/r06_${tag}_prof_c3 -o c3 -- python -u bench.py --no-cpu --steps 10 --warmup 3 || exit $? ;;
-    lat) run lat 300 python -u bench.py --workload latency || exit $? ;;
+    lat) run lat 300 python -u bench.py --full --workload latency || exit $? ;;
     ab_cross) AB_WORKLOADS="c3 c4" run ab_cross 1000 bash tools/ab_bench_libs.sh r06_ab_cross_inner _ab/libgpfit_crossbase.so _ab/libgpfit_crossnt.so || exit $? ;;
     t_sched) run t_sched 600 $PYT tests/test_gpu_sched.py tests/test_gpu_c3.py tests/test_gpu_c4.py || exit $? ;;
     ab_spec) run ab_spec 1000 bash -c 'for S in ${AB_SPECS:-2 3 4 4 3 2}; do echo "spec $S"; GPFIT_MCMC_SPEC=$S timeout -k 10 240 python -u bench.py --workload fit --no-cpu | tail -1 || exit 1; done' || exit $? ;;
