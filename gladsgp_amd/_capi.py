@@ -111,6 +111,10 @@ SIGNATURES = {
     "gp_field_max_pcs": (c_int, []),
     "gp_field": (c_int, [c_void_p, c_ll, c_int, c_int, c_void_p, c_ll, c_int, c_void_p,
                          c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
+    "gp_field_summary_max_tail": (c_int, []),
+    "gp_field_summary": (c_int, [c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_void_p, c_ll, c_int,
+                                 c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
+                                 c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

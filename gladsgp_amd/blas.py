@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -152,6 +153,98 @@ def field(W: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = None,
                err.data_ptr() if err is not None else None, out.data_ptr(), out.stride(0),
                int(f32), _stream(W.device))
     return out
+
+
+def field_summary_max_tail() -> int:
+    return int(_capi.lib().gp_field_summary_max_tail())
+
+
+def summary_tail_depths(S: int, q_lo: float, q_hi: float):
+    """Order statistics gp_field_summary keeps per tail for (S, q_lo, q_hi): the lower one reads
+    z_(j), z_(j+1) at j = floor(q_lo (S-1)), the upper one the same two counted from the top."""
+    jl = int(np.floor(q_lo * (S - 1)))
+    jh = int(np.floor(q_hi * (S - 1)))
+    return min(jl + 2, S), S - jh
+
+
+def _band(q):
+    """q -> (q_lo, q_hi): a float is the band [q, 1 - q]."""
+    if np.ndim(q) == 0:
+        return float(q), 1.0 - float(q)
+    q_lo, q_hi = q
+    return float(q_lo), float(q_hi)
+
+
+def field_summary(W3: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = None,
+                  mu: torch.Tensor | None = None, err: torch.Tensor | None = None, q=0.025,
+                  f32: bool = False, out=None):
+    """(mean, lo, hi) over the S samples of the field (W3 K + err) sd + mu in one pass
+    (gp_field_summary; np.mean(get_y(), 0) and np.quantile(get_y() + error, [q, 1 - q], 0) without
+    the (S, m, ncols) field): W3 (S, m, P) fp64 with unit last stride (its two leading strides are
+    passed through), K (P x ncols, row stride free), sd / mu (ncols) or both None, err (S m values,
+    sample-major) or None; ``q`` a float (band [q, 1 - q]) or a pair (q_lo, q_hi).  Each result is
+    (m, ncols), float32 when ``f32`` else float64; ``out`` = three such tensors (unit column
+    stride, one common row stride) to write into."""
+    for nm, t, nd in (("W3", W3, 3), ("K", K, 2)):
+        if not torch.is_tensor(t) or t.dtype != F64 or t.dim() != nd:
+            raise ValueError(f"field_summary: {nm} must be a {nd}-d float64 tensor")
+    S, m, P = W3.shape
+    dev = W3.device
+    if K.device != dev:
+        raise ValueError("field_summary: W3 and K must be on one device")
+    if S < 1 or P < 1 or K.shape[0] != P:
+        raise ValueError(f"field_summary: W3 {tuple(W3.shape)} needs S >= 1 samples and K "
+                         f"{tuple(K.shape)} one row per PC")
+    ncols = K.shape[1]
+    ldw = W3.stride(1) if m > 1 else max(W3.stride(1), P)
+    lds = W3.stride(0) if S > 1 else max(W3.stride(0), (m - 1) * ldw + P)
+    if (P > 1 and W3.stride(2) != 1) or ldw < P or lds < (max(m, 1) - 1) * ldw + P:
+        raise ValueError("field_summary: W3 needs a unit last stride and sample-major strides "
+                         f"(lds >= (m - 1) ldw + P, ldw >= P), got {W3.stride()}")
+    ldk = K.stride(0) if P > 1 else max(K.stride(0), ncols, 1)
+    if (ncols > 1 and K.stride(1) != 1) or ldk < max(ncols, 1):
+        raise ValueError(f"field_summary: K must be row-major (strides {K.stride()})")
+    if (sd is None) != (mu is None):
+        raise ValueError("field_summary: sd and mu go together")
+    for nm, t, n in (("sd", sd, ncols), ("mu", mu, ncols), ("err", err, S * m)):
+        if t is None:
+            continue
+        if t.dtype != F64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"field_summary: {nm} must be contiguous float64 on W3's device")
+        if t.numel() != n:
+            raise ValueError(f"field_summary: {nm} has {t.numel()} values, expected {n}")
+    q_lo, q_hi = _band(q)
+    if not (0.0 <= q_lo <= q_hi <= 1.0):
+        raise ValueError(f"field_summary: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
+    dt = torch.float32 if f32 else F64
+    if out is None:
+        out = tuple(torch.empty((m, ncols), dtype=dt, device=dev) for _ in range(3))
+    if len(out) != 3:
+        raise ValueError("field_summary: out is (mean, lo, hi)")
+    ldo = max(ncols, 1)
+    for t in out:
+        if not torch.is_tensor(t) or t.dtype != dt or t.device != dev or \
+                tuple(t.shape) != (m, ncols):
+            raise ValueError(f"field_summary: out tensors must be {dt} of shape {(m, ncols)} on "
+                             "W3's device")
+        if ncols > 1 and t.stride(1) != 1:
+            raise ValueError("field_summary: out tensors need a unit column stride")
+        if m > 1:
+            ldo = max(ldo, t.stride(0))
+    for t in out:
+        if m > 1 and t.stride(0) != ldo:
+            raise ValueError("field_summary: out tensors must share one row stride >= ncols")
+    mean, lo, hi = out
+    if dev.type != "cuda":
+        raise ValueError("field_summary: the operands must be on a HIP device")
+    if m == 0 or ncols == 0:
+        return mean, lo, hi
+    _capi.call("gp_field_summary", W3.data_ptr(), ldw, lds, S, m, P, K.data_ptr(), ldk, ncols,
+               sd.data_ptr() if sd is not None else None,
+               mu.data_ptr() if mu is not None else None,
+               err.data_ptr() if err is not None else None, q_lo, q_hi, mean.data_ptr(),
+               lo.data_ptr(), hi.data_ptr(), ldo, int(f32), _stream(dev))
+    return mean, lo, hi
 
 
 def mean_var(x: torch.Tensor, ddof: int = 0):

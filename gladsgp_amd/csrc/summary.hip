@@ -1,0 +1,414 @@
+// Fused predictive summary (A9 + its reduction): mean and quantile band of the reconstructed
+// field over the posterior samples -- np.mean(preds.get_y(), 0) and np.quantile(preds.get_y() +
+// error, [q, 1 - q], 0) of assess_all_models.py:489-500 / 510-521, plot_test_error.py:77-87,
+// include_trunc_error.py:84-90 -- in one pass over w and K.  The (S, m, ny) field the reference
+// builds only to reduce it (four test points at a time, because it does not fit otherwise) is
+// never stored: 3 m ny outputs instead of S m ny.
+//
+// Layout: block = 4 waves; every wave owns 32 consecutive columns (two 16-column MFMA tiles),
+// the block 128.  A work unit is (column panel, test point); block i takes a contiguous range of
+// the panel-major unit list and keeps its K panel (the B operands of all k-steps) in registers
+// while the panel lasts, as field_kernel does.  The point's S rows of w (one per sample, stride
+// lds) stream through LDS in 32-sample tiles (16 at P > 32), double-buffered across unit
+// boundaries (the next tile's global loads in flight under the current tile's MFMAs); the
+// tile's error scalars ride in a spare column of the LDS rows.
+//
+// After a tile's MFMAs every lane folds its 2 x 8 accumulator values (MFMA C layout: lane l,
+// register r holds row (l >> 4) + 4 r, column l & 15 of a 16 x 16 tile) into running state per
+// owned column: one fp64 sum of y, the KT smallest z (ascending) and the KT smallest -z, i.e. the
+// KT largest z, both kept by min/max insertion in registers (2 KT - 1 operations per value and
+// list; rows past S in the last tile are branched around and enter nothing).  The
+// state is 2 KT + 1 doubles per column whatever S is.  At the end of a unit the four lanes that
+// share a column (l >> 4 = 0..3) merge by two cross-lane exchanges that also split the work:
+// lanes 16 apart trade tiles (one keeps column tile 0, the other tile 1), lanes 32 apart trade
+// tails (one keeps the lower list, the other the upper), so each of the 64 lanes ends with one
+// complete list of one column and does one interpolation.  No LDS is needed for the merge.
+//
+// Bits: a_s is field_kernel's k-ordered MFMA chain (same operands, same order), y and z are the
+// same fma / add as its epilogue, so every sample value equals gp_field's bit for bit; the order
+// statistics are selections of those values (exact), the interpolation is numpy's _lerp with its
+// three roundings (no contraction), the mean is a fixed-order fp64 sum divided by S.
+#include "gpfit_common.h"
+#include "../../include/gpfit.h"
+
+#include <math.h>
+
+namespace {
+
+// waves per SIMD the register allocator is asked to keep: 2 (256 registers per lane; the small
+// instantiations end below that and fit 3-4); the deepest lists (2 x 2 x 8 doubles of state
+// beside the K panel) get the whole file instead of spilling to scratch
+template <int KS, int KT> constexpr int sum_occ() { return KT > 4 || (KT == 4 && KS > 12) ? 1 : 2; }
+constexpr int kSumWaves = 4;                  // waves per block
+constexpr int kSumJT = 2;                     // 16-column MFMA tiles per wave
+constexpr int kSumThreads = 64 * kSumWaves;
+constexpr int kSumWaveCols = 16 * kSumJT;
+constexpr int kSumCols = kSumWaves * kSumWaveCols;   // output columns per block
+// samples per tile: 32 (two 16-row MFMA sub-tiles), 16 at P > 32 where the K panel (128 of the
+// 256 registers at P = 64) leaves no room for the second sub-tile's accumulators and staging
+template <int KS> constexpr int sum_rows() { return KS <= 8 ? 32 : 16; }
+constexpr int kSumPitch = 68;                 // LDS row pitch of a w tile (doubles)
+constexpr int kSumErrCol = 64;                // the row's error scalar (k < 64 are the weights)
+constexpr int kSumMaxP = 64;
+constexpr int kSumMaxTail = 8;
+
+// one tail of the band: the two list positions numpy's linear rule reads and its weight
+struct SumTail {
+  int ia, ib;
+  double t;
+};
+
+// sorted insertion: l ascending keeps the KT smallest of what it has seen; NEG inserts -v (the
+// source modifier is free).  v_min_f64 / v_max_f64 are written out because fmin / fmax add a
+// canonicalising v_max_f64 x, x, x per operand whose producer the compiler cannot see (every list
+// entry at every basic-block entry: +40 % fp64 operations in the fold), which values that all come
+// out of v_fma_f64 or of these two instructions do not need.
+template <int KT, bool NEG = false>
+GP_DEV void sum_insert(double (&l)[KT], double v) {
+#pragma unroll
+  for (int i = 0; i < KT; ++i) {
+    double w;                                  // the larger moves on, the smaller stays in place
+    if (NEG && i == 0) {
+      asm("v_max_f64 %0, %1, -%2" : "=v"(w) : "v"(l[i]), "v"(v));
+      asm("v_min_f64 %0, %0, -%1" : "+v"(l[i]) : "v"(v));
+    } else {
+      asm("v_max_f64 %0, %1, %2" : "=v"(w) : "v"(l[i]), "v"(v));
+      asm("v_min_f64 %0, %0, %1" : "+v"(l[i]) : "v"(v));
+    }
+    v = w;
+  }
+}
+
+// numpy's _lerp(a, b, t): every product and sum rounded on its own
+GP_DEV double sum_lerp(double a, double b, double t) {
+#pragma clang fp contract(off)
+  const double d = b - a;
+  const double up = a + d * t;
+  const double dn = b - d * (1.0 - t);
+  return t >= 0.5 ? dn : up;
+}
+
+// KS = k-steps of 4 (P <= 4 KS), KT = list depth per tail.  Work units are (column panel, test
+// point) pairs, panel-major; block i takes units [i U / B, (i + 1) U / B) of the U = npanels x m.
+template <int KS, int KT>
+__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kernel(
+    const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
+    const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
+    const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
+    void* __restrict__ mean, void* __restrict__ lo, void* __restrict__ hi, long long ldo,
+    int out_f32, int nts) {
+  constexpr int KP = 4 * KS;                               // padded inner dimension
+  constexpr int kSumRows = sum_rows<KS>(), RS = kSumRows / 16;
+  constexpr int NLD = (kSumRows * KP + kSumThreads - 1) / kSumThreads;   // per thread
+  __shared__ double ws[2][kSumRows * kSumPitch];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int li = lane & 15, lk = lane >> 4;
+  const long long npanels = (ncols + kSumCols - 1) / kSumCols;
+  const long long units = npanels * m;
+  const long long u0 = units * blockIdx.x / gridDim.x;
+  const long long u1 = units * (blockIdx.x + 1) / gridDim.x;
+  if (u0 >= u1) return;                                    // block-uniform
+  const double inf = __builtin_inf();
+
+  double b[KS][kSumJT];
+  long long cur = -1;                                      // the panel held in b
+  auto load_panel = [&](long long panel) {
+    const int c0 = (int)panel * kSumCols + wv * kSumWaveCols;   // this wave's first column
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int jt = 0; jt < kSumJT; ++jt) {
+        const int k = 4 * ks + lk, c = c0 + 16 * jt + li;
+        b[ks][jt] = (k < P && c < ncols) ? K[(long long)k * ldk + c] : 0.0;
+      }
+    cur = panel;
+  };
+
+  // tile ts of point i -> registers: element e = tid + 256 q is (sample row e / KP, k e % KP);
+  // the first kSumRows threads also fetch their row's error scalar
+  double pre[NLD], pre_e = -0.0;
+  auto load_tile = [&](int i, int ts) {
+    const int s0 = ts * kSumRows;
+    const double* wp = W + (long long)i * ldw;
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+      const int e = threadIdx.x + kSumThreads * q;
+      const int r = e / KP, k = e % KP;
+      pre[q] = (e < kSumRows * KP && k < P && s0 + r < S) ? wp[(long long)(s0 + r) * lds + k]
+                                                          : 0.0;
+    }
+    if (err && threadIdx.x < kSumRows)
+      pre_e = s0 + (int)threadIdx.x < S ? err[(long long)(s0 + (int)threadIdx.x) * m + i] : -0.0;
+  };
+  auto store_tile = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+      const int e = threadIdx.x + kSumThreads * q;
+      if (e < kSumRows * KP) ws[buf][(e / KP) * kSumPitch + e % KP] = pre[q];
+    }
+    if (threadIdx.x < kSumRows) ws[buf][threadIdx.x * kSumPitch + kSumErrCol] = pre_e;
+  };
+
+  // running state of the lane's two columns (tile jt, column li): rows lk + 4 q of every tile
+  double sum[kSumJT], lo_l[kSumJT][KT], nh_l[kSumJT][KT], s_c[kSumJT], m_c[kSumJT];
+  auto reset = [&](long long panel) {
+    const int c0 = (int)panel * kSumCols + wv * kSumWaveCols;
+#pragma unroll
+    for (int jt = 0; jt < kSumJT; ++jt) {
+      sum[jt] = 0.0;
+#pragma unroll
+      for (int i = 0; i < KT; ++i) lo_l[jt][i] = nh_l[jt][i] = inf;
+      const int c = c0 + 16 * jt + li;
+      // without sd / mu: fma(a, 1, -0) = a for every a, signed zeros included
+      const bool ok = sd != nullptr && c < ncols;
+      s_c[jt] = ok ? sd[c] : 1.0;
+      m_c[jt] = ok ? mu[c] : -0.0;
+    }
+  };
+
+  long long u = u0, panel = u0 / m;                        // unit u = panel * m + i
+  int i = (int)(u0 - panel * m), ts = 0, buf = 0;
+  load_tile(i, 0);
+  store_tile(0);
+  __syncthreads();
+  reset(panel);
+  for (;;) {
+    if (panel != cur) load_panel(panel);
+    int tsn = ts + 1, in = i;
+    long long un = u;
+    if (tsn == nts) {
+      tsn = 0;
+      ++un;
+      in = i + 1 == m ? 0 : i + 1;
+    }
+    const bool more = un < u1;
+    if (more) load_tile(in, tsn);                          // in flight under the MFMAs
+    f64x4 acc[RS][kSumJT];
+#pragma unroll
+    for (int rs = 0; rs < RS; ++rs)
+#pragma unroll
+      for (int jt = 0; jt < kSumJT; ++jt) acc[rs][jt] = zero4();
+    const double* wt = ws[buf];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+      for (int rs = 0; rs < RS; ++rs) {
+        const double a = wt[(16 * rs + li) * kSumPitch + 4 * ks + lk];
+#pragma unroll
+        for (int jt = 0; jt < kSumJT; ++jt)
+          acc[rs][jt] = mfma16x16x4(a, b[ks][jt], acc[rs][jt]);
+      }
+    }
+    // fold: sample row 16 rs + lk + 4 q of the tile, column 16 jt + li of the wave's panel
+    const int s0 = ts * kSumRows;
+    // (without err the scalar is -0: a + -0 = a for every a, as fma(a, 1, -0) = a without sd --
+    // one code path for all four operand combinations keeps the register budget).
+    // Rows past S are masked by the branch: their lanes execute none of the fold.
+#pragma unroll
+    for (int rs = 0; rs < RS; ++rs)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = 16 * rs + lk + 4 * q;
+        if (s0 + r < S) {
+          const double e = wt[r * kSumPitch + kSumErrCol];
+#pragma unroll
+          for (int jt = 0; jt < kSumJT; ++jt) {
+            const double a = acc[rs][jt][q];
+            const double y = fma(a, s_c[jt], m_c[jt]);
+            const double z = fma(a + e, s_c[jt], m_c[jt]);
+            sum[jt] += y;
+            sum_insert<KT>(lo_l[jt], z);
+            sum_insert<KT, true>(nh_l[jt], z);
+          }
+        }
+      }
+
+    if (tsn == 0) {
+      // the unit is complete.  Exchange 1 (lanes 16 apart): the even lk keeps column tile 0 and
+      // takes its partner's tile-0 state, the odd one tile 1.
+      const bool odd = lk & 1, up = lk >> 1;
+      double L[KT], N[KT], R[KT];
+#pragma unroll
+      for (int j = 0; j < KT; ++j) {
+        L[j] = odd ? lo_l[1][j] : lo_l[0][j];
+        R[j] = __shfl_xor(odd ? lo_l[0][j] : lo_l[1][j], 16);
+      }
+#pragma unroll
+      for (int j = 0; j < KT; ++j) sum_insert<KT>(L, R[j]);
+#pragma unroll
+      for (int j = 0; j < KT; ++j) {
+        N[j] = odd ? nh_l[1][j] : nh_l[0][j];
+        R[j] = __shfl_xor(odd ? nh_l[0][j] : nh_l[1][j], 16);
+      }
+#pragma unroll
+      for (int j = 0; j < KT; ++j) sum_insert<KT>(N, R[j]);
+      double sm = (odd ? sum[1] : sum[0]) + __shfl_xor(odd ? sum[0] : sum[1], 16);
+      // exchange 2 (lanes 32 apart): lk < 2 keeps the lower list, lk >= 2 the (negated) upper
+      double F[KT];
+#pragma unroll
+      for (int j = 0; j < KT; ++j) {
+        F[j] = up ? N[j] : L[j];
+        R[j] = __shfl_xor(up ? L[j] : N[j], 32);
+      }
+#pragma unroll
+      for (int j = 0; j < KT; ++j) sum_insert<KT>(F, R[j]);
+      sm = sm + __shfl_xor(sm, 32);
+      // the two order statistics of this lane's tail, its interpolation, the stores
+      const int ia = up ? thi.ia : tlo.ia, ib = up ? thi.ib : tlo.ib;
+      const double t = up ? thi.t : tlo.t;
+      double va = F[0], vb = F[0];
+#pragma unroll
+      for (int j = 1; j < KT; ++j) {
+        va = ia == j ? F[j] : va;
+        vb = ib == j ? F[j] : vb;
+      }
+      if (up) {
+        va = -va;
+        vb = -vb;
+      }
+      const double qv = sum_lerp(va, vb, t);
+      const int c = (int)panel * kSumCols + wv * kSumWaveCols + 16 * (int)odd + li;
+      if (c < ncols) {
+        const long long o = (long long)i * ldo + c;
+        void* qp = up ? hi : lo;
+        if (out_f32) {
+          static_cast<float*>(qp)[o] = static_cast<float>(qv);
+          if (!up) static_cast<float*>(mean)[o] = static_cast<float>(sm / (double)S);
+        } else {
+          static_cast<double*>(qp)[o] = qv;
+          if (!up) static_cast<double*>(mean)[o] = sm / (double)S;
+        }
+      }
+    }
+    if (!more) break;
+    store_tile(buf ^ 1);                                   // the other buffer: last read a tile ago
+    __syncthreads();
+    buf ^= 1;
+    if (tsn == 0) {
+      if (in == 0) ++panel;
+      reset(panel);
+    }
+    ts = tsn;
+    i = in;
+    u = un;
+  }
+}
+
+int summary_num_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+    return n;
+  }();
+  return ncu;
+}
+
+struct SumArgs {
+  const double* W;
+  long long ldw, lds;
+  int S, m, P;
+  const double* K;
+  long long ldk;
+  int ncols;
+  const double *sd, *mu, *err;
+  SumTail tlo, thi;
+  void *mean, *lo, *hi;
+  long long ldo;
+  int out_f32;
+  hipStream_t stream;
+};
+
+// blocks of an instantiation that fit a CU at once (registers and LDS, from the runtime)
+template <int KS, int KT>
+int summary_blocks_per_cu() {
+  static const int nb = [] {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, summary_kernel<KS, KT>, kSumThreads,
+                                                     0) != hipSuccess || n < 1)
+      n = sum_occ<KS, KT>();
+    return n;
+  }();
+  return nb;
+}
+
+template <int KS, int KT>
+hipError_t launch_summary(const SumArgs& a) {
+  const long long units = (long long)gp_ceil_div(a.ncols, kSumCols) * a.m;
+  const int nts = (a.S + sum_rows<KS>() - 1) / sum_rows<KS>();
+  // one residency round: no tail round of blocks
+  long long blocks = (long long)summary_num_cus() * summary_blocks_per_cu<KS, KT>();
+  if (blocks > units) blocks = units;
+  hipLaunchKernelGGL((summary_kernel<KS, KT>), dim3((unsigned)blocks), dim3(kSumThreads), 0,
+                     a.stream, a.W, a.ldw, a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu,
+                     a.err, a.tlo, a.thi, a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts);
+  return hipGetLastError();
+}
+
+template <int KT>
+hipError_t dispatch_summary_ks(const SumArgs& a) {
+  const int ks = (a.P + 3) / 4;
+  if (ks <= 2) return launch_summary<2, KT>(a);
+  if (ks <= 4) return launch_summary<4, KT>(a);
+  if (ks <= 8) return launch_summary<8, KT>(a);
+  if (ks <= 12) return launch_summary<12, KT>(a);
+  return launch_summary<16, KT>(a);
+}
+
+// numpy's "linear" rule: pos = q (S - 1), j = floor(pos), t = pos - j
+void summary_position(double q, int S, int* j, double* t) {
+  const double pos = q * (double)(S - 1);
+  const double f = floor(pos);
+  *j = (int)f;
+  *t = pos - f;
+}
+
+}  // namespace
+
+extern "C" int gp_field_summary_max_tail(void) { return kSumMaxTail; }
+
+extern "C" int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m, int P,
+                                const double* K, long long ldk, int ncols, const double* sd,
+                                const double* mu, const double* err, double q_lo, double q_hi,
+                                void* mean, void* lo, void* hi, long long ldo, int out_f32,
+                                hipStream_t stream) {
+  if (!W) return -1;
+  if (ldw < P || ldw < 1) return -2;
+  if (lds < 1 || lds < (m > 0 ? m - 1 : 0) * ldw + P) return -3;
+  if (S < 1) return -4;
+  if (m < 0) return -5;
+  if (P < 1 || P > kSumMaxP) return -6;
+  if (!K) return -7;
+  if (ldk < ncols || ldk < 1) return -8;
+  if (ncols < 0) return -9;
+  if ((sd == nullptr) != (mu == nullptr)) return -10;
+  if (!(q_lo >= 0.0 && q_lo <= 1.0)) return -13;
+  if (!(q_hi >= 0.0 && q_hi <= 1.0) || q_lo > q_hi) return -14;
+  // selection depth: the lower tail reads z_(j), z_(j+1) of the ascending order, the upper one
+  // the same two counted from the top
+  int jl, jh;
+  double tl, th;
+  summary_position(q_lo, S, &jl, &tl);
+  summary_position(q_hi, S, &jh, &th);
+  const int dlo = jl + 2 < S ? jl + 2 : S, dhi = S - jh;
+  if (dlo > kSumMaxTail) return -13;
+  if (dhi > kSumMaxTail) return -14;
+  if (!mean) return -15;
+  if (!lo) return -16;
+  if (!hi) return -17;
+  if (ldo < ncols || ldo < 1) return -18;
+  if (m == 0 || ncols == 0) return 0;
+  const int jl1 = jl + 1 < S ? jl + 1 : jl, jh1 = jh + 1 < S ? jh + 1 : jh;
+  // the upper list holds -z ascending: z_(j) is its entry S - 1 - j
+  const SumTail a_lo = {jl, jl1, jl1 == jl ? 0.0 : tl};
+  const SumTail a_hi = {S - 1 - jh, S - 1 - jh1, jh1 == jh ? 0.0 : th};
+  const SumArgs a = {W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, err, a_lo, a_hi,
+                     mean, lo, hi, ldo, out_f32, stream};
+  const int depth = dlo > dhi ? dlo : dhi;
+  const hipError_t e = depth <= 2   ? dispatch_summary_ks<2>(a)
+                       : depth <= 4 ? dispatch_summary_ks<4>(a)
+                                    : dispatch_summary_ks<8>(a);
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}

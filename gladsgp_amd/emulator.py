@@ -517,21 +517,7 @@ class EmulatorPrediction:
         mu = sd = None
         if not std:
             mu, sd = sd_.y_mean[c0:c1].contiguous(), sd_.y_sd[c0:c1].contiguous()
-        w2 = wd.reshape(S * m, P).contiguous()
-        if P <= blas.field_max_pcs():
-            # one pass: y = (w K + e) sd + mu, written once in the output dtype (K's column
-            # block read in place through its row stride)
-            y = blas.field(w2, sd_.K[:, c0:c1], sd, mu, e, f32=f32)
-        else:
-            K = sd_.K if (c0, c1) == (0, sd_.K.shape[1]) else sd_.K[:, c0:c1].contiguous()
-            Wc = CM.of_rowmajor(w2)                              # (P x S m)
-            Kc = CM.of_rowmajor(K)                               # (ny_r x P)
-            Yc = gemm(False, False, Kc, Wc)                      # (ny_r x S m) = (w K)^T
-            y = Yc.t[: S * m, : c1 - c0]                         # (S m, ny_r) row-major
-            if e is not None:
-                y = y + e.reshape(S * m, 1)                      # one scalar per row
-            if not std:
-                y = blas.standardize(y.contiguous(), mu, sd, inverse=True)
+        y = self._field_rows(wd.reshape(S * m, P).contiguous(), c0, c1, sd, mu, e, f32)
         if dist_on and gather:
             counts = [gdist.shard_range(sd_.K.shape[1], r, ctx.world) for r in range(ctx.world)]
             y = gdist.gather_cols(ctx, y.contiguous(), [b - a for a, b in counts])
@@ -540,6 +526,100 @@ class EmulatorPrediction:
         if not to_host:
             return y.reshape(S, m, -1)
         return _to_host(y.reshape(S, m, -1), out_dtype)
+
+    def _field_rows(self, w2: torch.Tensor, c0: int, c1: int, sd, mu, e, f32: bool):
+        """(w2 K[:, c0:c1] + e) sd + mu for rows x P weights (sd / mu None: standardised), on the
+        device: gp_field up to gp_field_max_pcs() PCs, the generic GEMM + back-transform (fp64)
+        beyond."""
+        sd_ = self.model.data.sim_data
+        rows, P = w2.shape
+        if P <= blas.field_max_pcs():
+            # one pass: y = (w K + e) sd + mu, written once in the output dtype (K's column
+            # block read in place through its row stride)
+            return blas.field(w2, sd_.K[:, c0:c1], sd, mu, e, f32=f32)
+        K = sd_.K if (c0, c1) == (0, sd_.K.shape[1]) else sd_.K[:, c0:c1].contiguous()
+        Wc = CM.of_rowmajor(w2)                              # (P x rows)
+        Kc = CM.of_rowmajor(K)                               # (ny_r x P)
+        Yc = gemm(False, False, Kc, Wc)                      # (ny_r x rows) = (w K)^T
+        y = Yc.t[:rows, : c1 - c0]                           # (rows, ny_r) row-major
+        if e is not None:
+            y = y + e.reshape(rows, 1)                       # one scalar per row
+        if sd is not None:
+            y = blas.standardize(y.contiguous(), mu, sd, inverse=True)
+        return y
+
+    def summary(self, q=0.025, std: bool = False, add_error: bool = True, rng=None,
+                per_point: bool = True, w=None, to_host: bool = True, out=None):
+        """(mean, lower, upper), each (m, ny): the mean of get_y() and the q / 1 - q quantiles
+        (``q`` a float, or a pair (q_lo, q_hi)) of get_y() + error over the posterior samples --
+        the loop body of assess_all_models.py:489-500 / plot_test_error.py:77-87 -- without the
+        (S, m, ny) field: one kernel (gp_field_summary) reads w and K once and writes the three
+        (m, ny) arrays.
+
+        The error draws are get_y(add_error=True, rng=..., per_point=...)'s (one error_draws call:
+        the same seed gives the same draws); the mean carries no error term, as in the reference.
+        The dtype follows get_y(): float32 after ``preds.w = preds.w.astype(np.float32)``.
+        ``out``: three device tensors (m, ny) of that dtype to write into; ``to_host=False``
+        returns device tensors.  With more than gp_field_max_pcs() PCs, or a tail deeper than
+        gp_field_summary_max_tail() order statistics, the field is built (fp64) in blocks of test
+        points of at most 1 GiB and reduced with torch.sort / mean: the same results to rounding.
+        Distributed predictions: computed on rank 0 (which holds w), None on the other ranks."""
+        ctx = self.ctx
+        if ctx is not None and ctx.distributed and ctx.rank != 0:
+            return None
+        sd_ = self.model.data.sim_data
+        dev = self.model.device
+        S, m, P = self.S, self.m, self.P
+        ny = sd_.K.shape[1]
+        f32 = w is None and self._w_dtype == np.float32
+        wd = (self.w_dev if w is None else _to_device_f64(w, dev)).contiguous()
+        q_lo, q_hi = blas._band(q)
+        if not (0.0 <= q_lo <= q_hi <= 1.0):
+            raise ValueError(f"summary: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
+        e = None
+        if add_error:
+            e = torch.as_tensor(self.error_draws(rng, per_point), dtype=F64, device=dev)
+            e = (e.expand(S, m) if e.shape[1] == 1 else e).reshape(S * m).contiguous()
+        mu = sd = None
+        if not std:
+            mu, sd = sd_.y_mean.contiguous(), sd_.y_sd.contiguous()
+        dt = torch.float32 if f32 else F64
+        if out is None:
+            out = tuple(torch.empty((m, ny), dtype=dt, device=dev) for _ in range(3))
+        if P <= blas.field_max_pcs() and \
+                max(blas.summary_tail_depths(S, q_lo, q_hi)) <= blas.field_summary_max_tail():
+            blas.field_summary(wd, sd_.K, sd, mu, e, q=(q_lo, q_hi), f32=f32, out=out)
+        else:
+            self._summary_blocks(wd, sd, mu, e, q_lo, q_hi, out)
+        if not to_host:
+            return out
+        return tuple(_to_host(t, np.float32 if f32 else np.float64) for t in out)
+
+    def _summary_blocks(self, wd, sd, mu, e, q_lo, q_hi, out) -> None:
+        """summary()'s generic route: the fp64 field of a block of test points (at most 1 GiB),
+        its mean and, from the sorted samples, numpy's linear-rule quantiles."""
+        S, m, P = wd.shape
+        ny = self.model.data.sim_data.K.shape[1]
+        mb = max(1, (1 << 30) // max(1, 8 * S * ny))
+        ev = None if e is None else e.reshape(S, m)
+        for a in range(0, m, mb):
+            b = min(m, a + mb)
+            w2 = wd[:, a:b].reshape(S * (b - a), P).contiguous()
+            y = self._field_rows(w2, 0, ny, sd, mu, None, False).reshape(S, b - a, ny)
+            out[0][a:b] = y.mean(dim=0)
+            if ev is not None:
+                del y
+                eb = ev[:, a:b].reshape(S * (b - a)).contiguous()
+                y = self._field_rows(w2, 0, ny, sd, mu, eb, False).reshape(S, b - a, ny)
+            z = torch.sort(y, dim=0).values
+            del y
+            for qq, dst in ((q_lo, out[1]), (q_hi, out[2])):
+                pos = qq * (S - 1)
+                j = int(np.floor(pos))
+                t = pos - j
+                lo_v, hi_v = z[j], z[min(j + 1, S - 1)]
+                d = hi_v - lo_v
+                dst[a:b] = lo_v + d * t if t < 0.5 else hi_v - d * (1.0 - t)
 
 
 def assemble_units(ctx, mean_l: torch.Tensor, var_l: torch.Tensor, n_units: int):

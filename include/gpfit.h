@@ -436,6 +436,29 @@ int gp_field(const double* W, long long ldw, int rows, int P, const double* K, l
              int ncols, const double* sd, const double* mu, const double* err, void* Y,
              long long ldy, int out_f32, hipStream_t stream);
 
+/* Predictive summary of the reconstructed field over the posterior samples, the reduction every
+ * consumer of get_y() applies at once (assess_all_models.py:489-500, 510-521,
+ * plot_test_error.py:77-87, include_trunc_error.py:84-90), in one pass that never stores the
+ * (S, m, ncols) field.  With a_s = sum_j W[s*lds + i*ldw + j] K[j*ldk + c] (gp_field's MFMA chain,
+ * bit for bit), y_s = a_s sd[c] + mu[c] and z_s = (a_s + err[s*m + i]) sd[c] + mu[c] (z_s = y_s
+ * when err is NULL; sd and mu NULL together: the standardised field), for i < m, c < ncols:
+ *   mean[i*ldo + c] = fp64 mean of y_s over s < S (no error term, as in the reference),
+ *   lo / hi[i*ldo + c] = the q_lo / q_hi quantile of z_s over s, numpy's default ("linear") rule:
+ *     pos = q (S - 1), j = floor(pos), t = pos - j, z_(j) + (z_(j+1) - z_(j)) t for t < 0.5,
+ *     z_(j+1) - (z_(j+1) - z_(j)) (1 - t) otherwise, z_(j) at j = S - 1,
+ * each rounded once to float32 (out_f32 = 1) or stored as fp64.  The order statistics are
+ * selections kept in registers: the lower tail needs the min(floor(q_lo (S-1)) + 2, S) smallest
+ * values, the upper one the S - floor(q_hi (S-1)) largest, each at most
+ * gp_field_summary_max_tail() = 8 (q = 0.025 up to S = 128); a deeper request returns the
+ * argument number of its q (-13 / -14) with nothing launched, as does q outside [0, 1] and
+ * q_lo > q_hi (-14).  -6 for P outside [1, gp_field_max_pcs()], -3 for lds < (m - 1) ldw + P;
+ * NaN samples are not ordered (unspecified quantiles).  m = 0 or ncols = 0: no launch. */
+int gp_field_summary_max_tail(void);
+int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m, int P,
+                     const double* K, long long ldk, int ncols, const double* sd,
+                     const double* mu, const double* err, double q_lo, double q_hi, void* mean,
+                     void* lo, void* hi, long long ldo, int out_f32, hipStream_t stream);
+
 /* out[0] = mean(x), out[1] = var(x, ddof) of a length-N vector (two-pass, deterministic);
  * work holds 1024 doubles.  np.var of the PC truncation residual, src/model.py:222. */
 int gp_mean_var(const double* x, long long N, int ddof, double* out, double* work,
