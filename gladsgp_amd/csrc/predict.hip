@@ -34,12 +34,15 @@ constexpr int BK = 16;    // K step
 constexpr long long kDefaultChunkElems = 256ll << 20;  // <= 2 GB of Kt per chunk
 constexpr int kDefaultChunk = 8192;                   // test points per chunk (batches)
 constexpr int kDefaultChunkSingle = 16384;            // ... and for one GP
-// Non-temporal cross-covariance stores (the chunk, 2.15 GB at C4, is read back by the TRMM from
-// HBM either way): C4 59.1-59.6 -> 58.7-58.8 ms per step, C3 unchanged
-// (profiles/r06/r06ai_ab_cross_nt.log)
-#ifndef CROSS_NT
-#define CROSS_NT 1
-#endif
+
+constexpr long long align256(long long bytes) { return ((bytes + 255) / 256) * 256; }
+
+// in an entry point: a HIP error ends the call with its C-ABI code
+#define GP_CK(x)                                            \
+  do {                                                      \
+    const hipError_t e_ = (x);                              \
+    if (e_ != hipSuccess) return GPFIT_ERR_HIP - (int)e_;   \
+  } while (0)
 
 // Cross-covariance chunk, k-major as the TRMM streams it:
 //   Kt[k * mc + c] = s * exp(-sum beta (X[k] - Xs[c])^2)
@@ -89,13 +92,11 @@ __global__ __launch_bounds__(256) void cross_kp_kernel(
     // exp unconditionally, then select: padding rows / columns have finite (zeroed) inputs,
     // and a conditional exp costs an exec-mask branch around each call
     const double v0 = sb * exp_neg_tab(e0, tab), v1 = sb * exp_neg_tab(e1, tab);
-#if CROSS_NT
+    // non-temporal stores (the chunk, 2.15 GB at C4, is read back by the TRMM from HBM either
+    // way): C4 59.1-59.6 -> 58.7-58.8 ms per step, C3 unchanged
+    // (profiles/r06/r06ai_ab_cross_nt.log)
     __builtin_nontemporal_store((col_ok && k < n) ? v0 : 0.0, o + (long long)k * mc + c);
     __builtin_nontemporal_store((col_ok && k + 1 < n) ? v1 : 0.0, o + (long long)(k + 1) * mc + c);
-#else
-    o[(long long)k * mc + c] = (col_ok && k < n) ? v0 : 0.0;
-    o[(long long)(k + 1) * mc + c] = (col_ok && k + 1 < n) ? v1 : 0.0;
-#endif
   }
 }
 
@@ -152,29 +153,9 @@ GP_DEV void trmm_stage(const double* __restrict__ As, const double* __restrict__
   }
 }
 
-// blockIdx.x -> (pair p, panel C).  Blocks b and b + 8 share an XCD (dispatch is round-robin
-// over the 8 XCDs), so with kXcdPanels = G > 0 the blocks of XCD slot x = b % 8 are laid out in
-// its own order t = b / 8 as groups of G panels (x, x + 8, ...) x all pairs, pair-major.  An
-// XCD's 64 resident blocks then hold G panels x 64/G pairs: each K* panel is read by 64/G
-// blocks at once and each L^-1 pair by G.  G = 0: pair-major over all panels (p = b / NC,
-// i.e. 16 panels x 4 pairs per XCD at C3, the K* panels re-fetched in every residency round).
-// C3 TRMM fabric traffic (FETCH_SIZE x2): G = 0 5.09 GB per launch, G = 4 4.52, G = 8 4.18;
-// launch time unchanged (profiles/r03/ab_map.log).
-#ifndef TRMM_XCD_PANELS
-#define TRMM_XCD_PANELS 8
-#endif
-constexpr int kXcdPanels = TRMM_XCD_PANELS;
-// Diagonal-block steps (timing experiments only; 0 is the library): 1 = every MFMA of the step
-// (exact for the padded layout, whose upper triangle is zero), 2 = none (wrong results)
-#ifndef TRMM_DIAG_MODE
-#define TRMM_DIAG_MODE 0
-#endif
-// XCD-local (problem, pair) units for batched launches (A/B build only): C4 TRMM 4.090 vs
-// 4.105-4.125 ms per launch, but 9.44 vs 5.47 GB of fabric traffic per launch (every K* panel
-// fetched by four XCDs; profiles/r05/r05m_umap.log, r05n_pmc_c4.log): not the default
-#ifndef TRMM_UNIT_MAP
-#define TRMM_UNIT_MAP 0
-#endif
+// Panels per group of the pair blocks' XCD-aware order (trmm_block_tiles)
+constexpr int kXcdPanels = 8;
+static_assert(kXcdPanels > 0, "the XCD-aware order deals whole groups of panels");
 
 // The tile-packed L^-1 (GPFIT_LINV_PACKED, the single-GP broadcast's payload): column k of the
 // padded npad x npad L^-1 from row 16 floor(k / 16) on, columns one after another, so every
@@ -216,12 +197,7 @@ struct TrmmArgs {
   int Gp;                  // panels g < Gp: row-tile pair blocks (uniform 8 (NI + 1) K steps)
   int Gx;                  //   ... of which g < Gx (a multiple of 8 kXcdPanels) in the XCD order
   int Qc;                  // panels g >= Gp: one block per tile, longest tiles first
-  int umap;                // batched launches: XCD-local (problem, pair) units (trmm_sched)
 };
-
-// A tile's K order: the second tile of a row-tile pair (I < NI - 1 - I) runs its diagonal block
-// first (kDiagFirst, below); every other tile runs k = 0, 1, ... .
-GP_DEV bool trmm_diag_first(int I, int NI);
 
 // blockIdx.x -> (panel g, first tile I0, second tile I1 or -1).
 //  * Pair blocks (bid < Gp NP): tiles (NI-1-p, g) then (p, g).  The first Gx panels in the
@@ -240,16 +216,7 @@ GP_DEV void trmm_block_tiles(int bid, const TrmmArgs& a, int& g, int& I0, int& I
   const int nA = a.Gp * NP;
   if (bid < nA) {
     int p;
-    if (a.umap) {
-      // unit u = (problem b, pair p) = u / NP, u % NP; XCD slot x takes units x, x + 8, ...,
-      // each over all NCt panels of the launch in turn (t = bid / 8): one XCD's resident blocks
-      // share one problem's pair p, i.e. two row tiles of L^-1 (<= 2 MB at n = 1024), where
-      // problem-major panels spread a whole 8 MB L^-1 over every XCD's 4 MB L2
-      const int x = bid & 7, t = bid >> 3, q = t / a.NCt;
-      const int u = x + 8 * q, C = t - q * a.NCt;
-      p = u % NP;
-      g = (u / NP) * a.NCt + C;
-    } else if (bid < a.Gx * NP) {
+    if (bid < a.Gx * NP) {
       const int x = bid & 7, t = bid >> 3, per = kXcdPanels * NP;
       const int grp = t / per, j = t - grp * per;
       p = j / kXcdPanels;
@@ -262,7 +229,9 @@ GP_DEV void trmm_block_tiles(int bid, const TrmmArgs& a, int& g, int& I0, int& I
     I0 = a.NI - 1 - p;
     I1 = (I0 == p) ? -1 : p;
     // (pair-order mixes -- reversed pairs in every other XCD group or block, or the pair's
-    // diagonal-first tile first -- measured no different, profiles/r05/r05f_ab.log)
+    // diagonal-first tile first -- measured no different, profiles/r05/r05f_ab.log; XCD-local
+    // (problem, pair) units for batches: C4 TRMM 4.090 vs 4.105-4.125 ms per launch but 9.44
+    // vs 5.47 GB of fabric traffic, every K* panel fetched by four XCDs, r05m_umap.log)
   } else {
     const int t = bid - nA;
     const int q = t / a.Qc;
@@ -272,18 +241,14 @@ GP_DEV void trmm_block_tiles(int bid, const TrmmArgs& a, int& g, int& I0, int& I
   }
 }
 
-// kDiagFirst: the second tile of a pair runs its diagonal block first.  A diagonal block's steps
+// A tile's K order: the second tile of a row-tile pair (I < NI - 1 - I) runs its diagonal block
+// first; every other tile runs k = 0, 1, ... .  A diagonal block's steps
 // carry few MFMAs (row tile r only meets L^-1 at steps t <= r) and are bound by the next
 // stage's load latency; with both tiles ending on their diagonal block every block of a
 // residency round spent its last 8 steps there together (all co-resident blocks at once), while
 // now pair p's two diagonal blocks sit back to back around step 8(NI - p), spread over the round.
 // Measured: C4 TRMM 2.059 -> 2.051 ms per launch, C3 unchanged (profiles/r03/ab_df.log).
-#ifndef TRMM_DIAG_FIRST
-#define TRMM_DIAG_FIRST 1
-#endif
-constexpr bool kDiagFirst = TRMM_DIAG_FIRST;
-
-GP_DEV bool trmm_diag_first(int I, int NI) { return kDiagFirst && 2 * I < NI - 1; }
+GP_DEV bool trmm_diag_first(int I, int NI) { return 2 * I < NI - 1; }
 
 // Row-tile pairs: block (p, g) computes tile (NI-1-p, g) and then tile (p, g), so every pair
 // block runs 8(NI+1) K steps (uniform work: at C3 the 512 blocks of a residency round finish
@@ -352,9 +317,7 @@ __global__ __launch_bounds__(256, 2) void trmm_pair_kernel(const TrmmArgs a) {
         else if (nst > BI / BK) issue(L, 0, smem + ((s + 1) & 1) * STAGE);
         else if (pass + 1 < npass)               // (a diagonal-only first tile) next tile's
           issue(Lb + Isecond * BI, first_step(Isecond), smem);   // first stage
-        if (TRMM_DIAG_MODE == 1) trmm_stage<false>(cur, cur + ASTAGE, acc, wr, wc, li, lk, 0);
-        else if (TRMM_DIAG_MODE == 0 && s <= 7 - wr)
-          trmm_stage<true>(cur, cur + ASTAGE, acc, wr, wc, li, lk, s);
+        if (s <= 7 - wr) trmm_stage<true>(cur, cur + ASTAGE, acc, wr, wc, li, lk, s);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
@@ -382,9 +345,7 @@ __global__ __launch_bounds__(256, 2) void trmm_pair_kernel(const TrmmArgs a) {
         else if (pass + 1 < npass)               // next tile's first stage
           issue(Lb + Isecond * BI, first_step(Isecond), smem);
         const int t = s - s_diag;               // the wave's last row tile is 7 - wr
-        if (TRMM_DIAG_MODE == 1) trmm_stage<false>(cur, cur + ASTAGE, acc, wr, wc, li, lk, 0);
-        else if (TRMM_DIAG_MODE == 0 && t <= 7 - wr)
-          trmm_stage<true>(cur, cur + ASTAGE, acc, wr, wc, li, lk, t);
+        if (t <= 7 - wr) trmm_stage<true>(cur, cur + ASTAGE, acc, wr, wc, li, lk, t);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
@@ -438,8 +399,8 @@ __global__ __launch_bounds__(256, 2) void trmm_pair_kernel(const TrmmArgs a) {
 // trip through HBM (the cross-covariance chunk written, then read by every row-tile pair).
 // Here a panel is kResCols = 64 test points of one problem, and one block computes ALL npad
 // rows of V = L^-1 K*^T for it:
-//   * K*'s panel passes through a 2 RES_AHEAD-chunk LDS ring (6 chunks, 96 KB), produced 32
-//     rows (a chunk) at a time, RES_AHEAD chunks ahead, by the block's own threads:
+//   * K*'s panel passes through a 2 kResAhead-chunk LDS ring (6 chunks, 96 KB), produced 32
+//     rows (a chunk) at a time, kResAhead chunks ahead, by the block's own threads:
 //     s exp(-sum (sqrt(beta)(x_k - x*_j))^2) with cross_kp_kernel's exact arithmetic (the same
 //     Kt values bit for bit), one exp per element -- no cross-covariance kernel, no Kt slab in
 //     HBM;
@@ -448,7 +409,9 @@ __global__ __launch_bounds__(256, 2) void trmm_pair_kernel(const TrmmArgs a) {
 //     registers as MFMA A fragments by buffer loads (wave-uniform offset + four per-lane
 //     offsets: no vector address arithmetic), one 16-k step ahead;
 //   * 8 waves, wave w owning the 16-row tiles {w, 15 - w, 16 + w, 31 - w} (the first RT of
-//     them: equal sums of (T + 1), i.e. equal MFMA work), all four 16-column MFMA tiles;
+//     them: equal sums of (T + 1), i.e. equal MFMA work), all four 16-column MFMA tiles
+//     (4 RT waves of two tiles each, 4 per SIMD at npad = 512, took the same time from slabs
+//     and spilled when fused: profiles/r06/r06v_w_res_variants.txt);
 //   * tile T meets L^-1 at k-steps j <= T; activity is resolved per chunk (steps 2c, 2c + 1:
 //     tile i takes part when T_i >= 2c, its step 2c + 1 then reading, when T_i = 2c, the zero
 //     16 x 16 block above the diagonal -- zeroed by gp_potrf_inv / gp_trtri; the packed layout
@@ -458,44 +421,24 @@ __global__ __launch_bounds__(256, 2) void trmm_pair_kernel(const TrmmArgs a) {
 //   * one block per panel (a persistent form that streamed a block's panels as one chunk
 //     sequence, loading the next panel's inputs under the last chunks, measured no faster:
 //     profiles/r06/r06ah_ab_res_persistent.log);
-//   * one barrier per RES_AHEAD chunks, one more per panel for the epilogue, which reduces
+//   * one barrier per kResAhead chunks, one more per panel for the epilogue, which reduces
 //     sum V z and sum V^2 over the panel's rows and writes mean / var directly (no slab, no
 //     finalize).
 // Every global load is issued unconditionally (at a clamped in-bounds address when its value
 // is not needed): the same number of loads on every path keeps the compiler's vmcnt waits
 // counted, so prefetches stay in flight across the MFMAs.
 // SLAB: K* read from a materialised cross-covariance chunk instead (gp_predict_solve after
-// gp_predict_cross, and d > 8), RES_AHEAD chunks ahead through registers -- the same Kt
+// gp_predict_cross, and d > 8), kResAhead chunks ahead through registers -- the same Kt
 // values, so every entry point gives the same bits at npad <= 512.
 // Sums run k ascending in every tile (the pair kernel runs some tiles diagonal-block first), so
 // results equal the pair path to rounding, not bit for bit; they do not depend on the chunking.
-#ifndef RES_COLS
-#define RES_COLS 64
-#endif
-#ifndef RES_OCC
-#define RES_OCC 2                              // waves per SIMD (launch bound)
-#endif
-constexpr int kResCols = RES_COLS;             // test points per panel
-// RES_WIDE: 4 RT waves of two row tiles each (16 waves at npad = 512: 4 per SIMD); else 8
-// waves of RT tiles
-#ifndef RES_WIDE
-#define RES_WIDE 0
-#endif
-// timing probes only (wrong results): 1 = no MFMAs, 2 = A fragments loaded once, 3 = no
-// chunk barriers, 5 = no K* production in the chunks, 6 = neither production nor barriers
-#ifndef RES_PROBE
-#define RES_PROBE 0
-#endif
-#ifndef RES_XCD
-#define RES_XCD 1
-#endif
-// RES_AHEAD = KA: K* produced KA chunks ahead into a 2 KA-slot LDS ring, design rows staged
-// 2 KA chunks ahead, one barrier per KA chunks
-#ifndef RES_AHEAD
-#define RES_AHEAD 3
-#endif
-__host__ __device__ constexpr int res_waves(int RT) { return RES_WIDE ? 4 * RT : 8; }
-constexpr int kResMaxWaves = 16;
+constexpr int kResCols = 64;                   // test points per panel
+constexpr int kResOcc = 2;                     // waves per SIMD (launch bound)
+constexpr int kResWaves = 8;                   // waves per block, each owning RT row tiles
+// kResAhead = KA: K* produced KA chunks ahead into a 2 KA-slot LDS ring, design rows staged
+// 2 KA chunks ahead, one barrier per KA chunks (KA = 2 2.556-2.566, KA = 3 2.507-2.525, KA = 4
+// 2.542-2.549 ms per launch: profiles/r06/r06as_ab_res_ahead.log)
+constexpr int kResAhead = 3;
 constexpr int kResMaxPad = 512;
 constexpr int kResD = 8;                       // design dimensions (d <= 8)
 
@@ -524,11 +467,10 @@ struct ResArgs {
 };
 
 template <bool PACKED, int RT, bool SLAB>
-__global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void trmm_res_kernel(
-    const ResArgs a) {
-  constexpr int NW = res_waves(RT);            // waves
+__global__ __launch_bounds__(64 * kResWaves, kResOcc) void trmm_res_kernel(const ResArgs a) {
+  constexpr int NW = kResWaves;                // waves, RT 16-row tiles each
+  constexpr int TW = RT;                       // 16-row tiles per wave
   constexpr int kResThreads = 64 * NW;
-  constexpr int TW = RT * 8 / NW;              // 16-row tiles per wave
   constexpr int NPAD = 128 * RT;
   constexpr int NCH = NPAD / 32;               // 32-row K* chunks per panel (even)
   constexpr int NJ = NPAD / 16;                // 16-k steps per panel
@@ -536,17 +478,13 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
   constexpr int BCH = 32 * kResCols;           // one chunk of K*
   constexpr int NCT = kResCols / 16;           // 16-column MFMA tiles per panel
   constexpr int NPR = kResThreads / kResCols;  // K* rows one production pass covers
-  constexpr int NH = (32 + NPR - 1) / NPR;     // production passes per chunk
-  constexpr bool RAG = 32 % NPR != 0;          // (the last pass covers part of the chunk)
-  constexpr int KA = RES_AHEAD;                // K* production distance (chunks)
+  constexpr int NH = 32 / NPR;                 // production passes per chunk
+  static_assert(32 % NPR == 0, "production passes cover whole chunks");
+  constexpr int KA = kResAhead;                // K* production distance (chunks)
   constexpr int KSL = 2 * KA;                  // K* ring slots
   // design-row staging distance: rows written at chunk c are read when chunk c + XA - KA
   // produces from them (needs XA >= 2 KA) and overwrite rows read at c + XA - 8 - KA (XA <= 8)
-#ifdef RES_XA
-  constexpr int XA = RES_XA;
-#else
   constexpr int XA = 2 * KA;
-#endif
   static_assert(XA >= 2 * KA && XA <= 8, "design-row ring has 8 slots");
   __shared__ __attribute__((aligned(16))) double Bs[KSL * BCH];   // K* chunks c .. c + KSL - 1
   __shared__ double tab[64];
@@ -555,13 +493,10 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
   double* const red = Bs;                      // epilogue partial sums (K* ring is done)
   static_assert(NW * 2 * kResCols <= KSL * BCH, "epilogue sums alias the K* ring");
   __shared__ double zs[NPAD];
-  // RES_XCD: the panels one XCD is dealt (blockIdx.x % 8 equal) are consecutive logical
-  // panels, so a problem's L^-1 is fetched into one XCD's L2 instead of all eight
-#if RES_XCD
+  // the panels one XCD is dealt (blockIdx.x % 8 equal) are consecutive logical panels, so a
+  // problem's L^-1 is fetched into one XCD's L2 instead of all eight (616 -> 88 MB per C5
+  // launch, time unchanged: profiles/r06/r06ao_pmc_res_traffic_xcd.txt, r06ao_ab_res_xcd.log)
   const int g = xcd_remap(blockIdx.x, gridDim.x);
-#else
-  const int g = blockIdx.x;
-#endif
   const int b = g / a.npanel, P = g - b * a.npanel;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -585,10 +520,7 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
     return (32 * c + xrow < a.n && xd < a.d) ? v * bq : 0.0;
   };
   const double* ktc = a.kt + b * a.sK + P * kResCols + pc;    // SLAB: column pc's chunk
-  auto kval = [&](int c, int h) {
-    const int r = rp + NPR * h;
-    return ktc[(long long)(32 * c + (RAG && r >= 32 ? 31 : r)) * a.mc];
-  };
+  auto kval = [&](int c, int h) { return ktc[(long long)(32 * c + rp + NPR * h) * a.mc]; };
   // K* chunk c in slot c & 1; row r's 64 doubles with the 16-column halves of each 32-column
   // group swapped in odd rows: the 16-lane groups of a B fragment read (rows k .. k+3) then
   // cover all 64 banks twice, conflict-free
@@ -601,7 +533,6 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
   // element h of chunk c of K*, from design-row slot `slot`
   auto produce_one = [&](int c, int slot, int h) {
     const int r = rp + NPR * h, k = 32 * c + r;
-    if (RAG && r >= 32) return;
     const double* xc = xsc + pc;               // [dim][point]: consecutive lanes, banks
     const double* xk = xring + slot * RING + r * kResD;
     double e = 0.0;
@@ -650,16 +581,9 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) bv[ct] = br[(16 * ct + li) ^ sw];
         static_for<decltype(F)::value, TW, 1>([&](auto I) {
-#if RES_PROBE != 1
 #pragma unroll
           for (int ct = 0; ct < NCT; ++ct) acc[I][ct] = mfma16x16x4(av[I][q], bv[ct], acc[I][ct]);
-#else
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct) acc[I][ct][0] += av[I][q] * bv[ct];
-#endif
-#if RES_PROBE != 2
           av[I][q] = frag(I, jn, q);
-#endif
         });
       }
     }
@@ -673,7 +597,7 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
       for (int c = 0; c < KA; ++c)
 #pragma unroll
         for (int h = 0; h < NH; ++h)
-          if (c < NCH && (!RAG || rp + NPR * h < 32)) *bslot(c, h) = kval(c, h);
+          if (c < NCH) *bslot(c, h) = kval(c, h);
     } else {
       if (tid < 64) tab[tid] = kExp2Tab[tid];
       double xs[kResCols / 32];                // test points xrow + 32 h, dimension xd
@@ -731,23 +655,18 @@ __global__ __launch_bounds__(64 * res_waves(RT), RES_WIDE ? RT : RES_OCC) void t
     } else {
       xn = xval(cf);
     }
-#if RES_PROBE != 5 && RES_PROBE != 6
     if (!SLAB && c + KA < NCH) produce(c + KA, (c + KA) & 7);
-#endif
     mstep(F, 2 * c);
     mstep(F, 2 * c + 1);
     if (SLAB) {
       if (c + KA < NCH) {
 #pragma unroll
-        for (int h = 0; h < NH; ++h)
-          if (!RAG || rp + NPR * h < 32) *bslot(c + KA, h) = kn[h];
+        for (int h = 0; h < NH; ++h) *bslot(c + KA, h) = kn[h];
       }
     } else {
       xring[(tid < RING ? (cf & 7) : 8) * RING + (tid & (RING - 1))] = xscale(cf, xn);
     }
-#if RES_PROBE != 3 && RES_PROBE != 6
     if (c % KA == KA - 1) __syncthreads();
-#endif
   };
   int c = 0;
   static_for<0, TW + 1, 1>([&](auto F) {
@@ -827,34 +746,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict_
   }
   mean[(long long)b * ldo + j] = sm;
   var[(long long)b * ldo + j] = s_pred[b] - sv;
-}
-
-template <int D>
-hipError_t cross_kp_launch_d(const double* X, int n, int ldx, const double* Xs, int mv,
-                             int ldxs, int d, const double* beta, int ldbeta, const double* s,
-                             double* Kt2, int mc, int npad, long long sK, int batch,
-                             hipStream_t st) {
-  // only the columns the chunk's TRMM reads (its ceil(mv / BC) column tiles; zeros past mv):
-  // the 1696-point tail chunk of C3 no longer computes all 16384 columns (14.7% of a step's
-  // cross-covariance work)
-  const int cols = min(mc, gp_ceil_div(mv, BC) * BC);
-  dim3 grid(gp_ceil_div(cols, 256), npad / 64, batch);
-  hipLaunchKernelGGL((cross_kp_kernel<D>), grid, dim3(256), 0, st, X, n, ldx, Xs, mv, ldxs, d,
-                     beta, ldbeta, s, Kt2, mc, sK);
-  return hipGetLastError();
-}
-
-hipError_t cross_kp_launch(const double* X, int n, int ldx, const double* Xs, int mv, int ldxs,
-                           int d, const double* beta, int ldbeta, const double* s, double* Kt2,
-                           int mc, int npad, long long sK, int batch, hipStream_t st) {
-  if (d <= 8)
-    return cross_kp_launch_d<8>(X, n, ldx, Xs, mv, ldxs, d, beta, ldbeta, s, Kt2, mc, npad, sK,
-                                batch, st);
-  if (d <= 16)
-    return cross_kp_launch_d<16>(X, n, ldx, Xs, mv, ldxs, d, beta, ldbeta, s, Kt2, mc, npad, sK,
-                                 batch, st);
-  return cross_kp_launch_d<32>(X, n, ldx, Xs, mv, ldxs, d, beta, ldbeta, s, Kt2, mc, npad, sK,
-                               batch, st);
 }
 
 // z = L^-1 w for the prediction in two deterministic passes (the same arithmetic whatever the
@@ -941,6 +832,7 @@ __global__ __launch_bounds__(256) void trmv_sum_kernel(const double* __restrict_
 }
 
 struct Plan {
+  int n, m, batch;         // the problem sizes the plan was made for
   int npad, NI, mc, NC, nchunks, slabs;
   long long off_z, off_zp, off_kt, off_part, off_pot, bytes, slab_elems, part_elems;
 };
@@ -954,6 +846,9 @@ struct Plan {
 Plan make_plan(int n, int m, int batch, int m_chunk, bool all_slabs = false,
                bool potrf = false) {
   Plan p;
+  p.n = n;
+  p.m = m;
+  p.batch = batch;
   p.npad = gp_padded_n(n);
   p.NI = p.npad / BI;
   const int mpad = gp_ceil_div(m, BC) * BC;
@@ -989,10 +884,10 @@ Plan make_plan(int n, int m, int batch, int m_chunk, bool all_slabs = false,
   p.part_elems = (long long)batch * 2 * p.NI * mc;
   const long long part = p.part_elems * p.slabs;
   p.off_z = 0;
-  p.off_zp = ((z * 8 + 255) / 256) * 256;
-  p.off_kt = p.off_zp + ((zp * 8 + 255) / 256) * 256;
-  p.off_part = p.off_kt + ((kt * 8 + 255) / 256) * 256;
-  p.off_pot = ((p.off_part + part * 8 + 255) / 256) * 256;
+  p.off_zp = align256(z * 8);
+  p.off_kt = p.off_zp + align256(zp * 8);
+  p.off_part = p.off_kt + align256(kt * 8);
+  p.off_pot = align256(p.off_part + part * 8);
   p.bytes = p.off_pot + (potrf ? gpfit_potrf_inv_ws_bytes(n, batch) : 0);
   return p;
 }
@@ -1032,14 +927,23 @@ int check_common(const double* X, int ldx, const double* Xs, int ldxs, int n, in
   return 0;
 }
 
+// L^-1 as the kernels load it (16-B double2 loads): -1 pointer, -2 leading dimension (at least
+// ld_min besides npad), -3 problem stride
+int check_linv(const double* Linv, int ldinv, long long strideInv, int n, int batch, bool packed,
+               int ld_min) {
+  if (!Linv || (reinterpret_cast<uintptr_t>(Linv) & 15)) return -1;
+  const int npad = gp_padded_n(n);
+  if (!packed && (ldinv < npad || ldinv < ld_min || (ldinv & 1))) return -2;
+  const long long per = packed ? linv_packed_elems(npad) : (long long)ldinv * npad;
+  if ((batch > 1 && strideInv < per) || (strideInv & 1)) return -3;
+  return 0;
+}
+
 int check_solve(const double* Linv, int ldinv, long long strideInv, int n, const double* s_pred,
                 const double* w_hat, int ldw, int m, double* mean, double* var, int ldo,
                 int batch, bool packed = false) {
-  if (!Linv || (reinterpret_cast<uintptr_t>(Linv) & 15)) return -1;
-  const int npad = gp_padded_n(n);
-  if (!packed && (ldinv < npad || ldinv < 1 || (ldinv & 1))) return -2;   // 16-B double2 loads
-  const long long per = packed ? linv_packed_elems(npad) : (long long)ldinv * npad;
-  if ((batch > 1 && strideInv < per) || (strideInv & 1)) return -3;
+  const int rc = check_linv(Linv, ldinv, strideInv, n, batch, packed, 1);
+  if (rc) return rc;
   if (!s_pred) return -14;
   if (!w_hat) return -15;
   if (ldw < n && batch > 1) return -16;
@@ -1070,32 +974,67 @@ struct LinvRef {
   bool packed;
 };
 
+// One prediction problem as the host side passes it on; an entry point fills these once, after
+// validation.  The sizes n, m, batch travel in the Plan.
+// The cross-covariance side: design and test points, hyper-parameters.  A solve from prepared
+// slabs (gp_predict_solve) has none.
+struct CrossSide {
+  const double* X;
+  int ldx;
+  const double* Xs;
+  int ldxs;
+  int d;
+  const double* beta;
+  int ldbeta;
+  const double* s;
+};
+// The solve side: L^-1, z = L^-1 w (problem stride zld) and the outputs.
+struct SolveSide {
+  LinvRef L;
+  const double* s_pred;
+  const double* z;
+  long long zld;
+  double *mean, *var;
+  int ldo;
+};
+
+// test points of chunk ch
+int chunk_cols(const Plan& p, int ch) { return min(p.m - ch * p.mc, p.mc); }
+
+// Chunk ch's cross-covariance into kt.
+hipError_t cross_chunk(const Plan& p, int ch, double* kt, const CrossSide& c,
+                       hipStream_t stream) {
+  const int mv = chunk_cols(p, ch);
+  // only the columns the chunk's TRMM reads (its ceil(mv / BC) column tiles; zeros past mv):
+  // the 1696-point tail chunk of C3 no longer computes all 16384 columns (14.7% of a step's
+  // cross-covariance work)
+  const int cols = min(p.mc, gp_ceil_div(mv, BC) * BC);
+  auto kern = cross_kp_kernel<8>;
+  if (c.d > 8) kern = c.d <= 16 ? cross_kp_kernel<16> : cross_kp_kernel<32>;
+  hipLaunchKernelGGL(kern, dim3(gp_ceil_div(cols, 256), p.npad / 64, p.batch), dim3(256), 0,
+                     stream, c.X, p.n, c.ldx, c.Xs + (long long)ch * p.mc * c.ldxs, mv, c.ldxs,
+                     c.d, c.beta, c.ldbeta, c.s, kt, p.mc, (long long)p.mc * p.npad);
+  return hipGetLastError();
+}
+
 // z = L^-1 w into z (npad rows per problem, problem stride zld), two passes through zp (the same
 // arithmetic whatever the chunking and the layout, so results stay bit-identical).
-hipError_t trmv_pred(int npad, double* zp, const LinvRef& L, const double* w_hat, int ldw,
-                     int n, int batch, double* z, long long zld, hipStream_t stream) {
-  const int nst = gp_ceil_div(npad, kZS);
-  const dim3 grid(gp_ceil_div(npad, kZR), nst, batch);
-  if (L.packed)
-    hipLaunchKernelGGL(trmv_part_kernel<true>, grid, dim3(256), 0, stream, L.p, L.ld, L.stride,
-                       w_hat, ldw, zp, npad, n);
-  else
-    hipLaunchKernelGGL(trmv_part_kernel<false>, grid, dim3(256), 0, stream, L.p, L.ld, L.stride,
-                       w_hat, ldw, zp, npad, n);
+hipError_t trmv_pred(const LinvRef& L, int n, int batch, const double* w_hat, int ldw,
+                     double* zp, double* z, long long zld, hipStream_t stream) {
+  const int npad = gp_padded_n(n), nst = gp_ceil_div(npad, kZS);
+  const auto part = L.packed ? trmv_part_kernel<true> : trmv_part_kernel<false>;
+  hipLaunchKernelGGL(part, dim3(gp_ceil_div(npad, kZR), nst, batch), dim3(256), 0, stream, L.p,
+                     L.ld, L.stride, w_hat, ldw, zp, npad, n);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(trmv_sum_kernel, dim3(gp_ceil_div(npad, 32), batch), dim3(256), 0,
                      stream, zp, nst, npad, n, z, zld);
   return hipGetLastError();
 }
-
-hipError_t cross_chunk(const Plan& p, int ch, double* kt, const double* X, int ldx,
-                       const double* Xs, int ldxs, int n, int m, int d, const double* beta,
-                       int ldbeta, const double* s, int batch, hipStream_t stream) {
-  const int c0 = ch * p.mc;
-  const int mv = (m - c0 < p.mc) ? (m - c0) : p.mc;
-  return cross_kp_launch(X, n, ldx, Xs + (long long)c0 * ldxs, mv, ldxs, d, beta, ldbeta, s, kt,
-                         p.mc, p.npad, (long long)p.mc * p.npad, batch, stream);
+// ... into the workspace's z (problem stride npad)
+hipError_t trmv_pred(const Plan& p, const WS& w, const LinvRef& L, const double* w_hat, int ldw,
+                     hipStream_t stream) {
+  return trmv_pred(L, p.n, p.batch, w_hat, ldw, w.zp, w.z, p.npad, stream);
 }
 
 // Residency slots of trmm_pair_kernel on the current device (CUs x blocks per CU), cached.
@@ -1138,155 +1077,160 @@ void trmm_sched(TrmmArgs& a, int batch, int slots) {
   a.Gp = (int)Gp;
   a.Qc = (int)(G - Gp);
   const int grp = 8 * kXcdPanels;
-  a.Gx = grp > 0 ? (a.Gp / grp) * grp : 0;
-  // XCD-local units for batches: every (problem, pair) unit spans whole launches' panels, and
-  // the units split evenly over the 8 XCD slots
-  a.umap = (TRMM_UNIT_MAP && batch > 1 && Gp == G && ((long long)batch * NP) % 8 == 0) ? 1 : 0;
+  a.Gx = (a.Gp / grp) * grp;
 }
 
 // The last chunk's TRMM runs merged with the one before it when its blocks fill less than one
 // residency round (the merged launch's schedule then packs that round with the previous
 // chunk's panels).
-bool trmm_merge_last(const Plan& p, int m, int batch) {
-  if (p.nchunks < 2 || m % p.mc == 0) return false;
-  const long long tail_panels = gp_ceil_div(m - (p.nchunks - 1) * p.mc, BC);
-  return (long long)batch * tail_panels * ((p.NI + 1) / 2) < trmm_slots();
+bool trmm_merge_last(const Plan& p) {
+  if (p.nchunks < 2 || p.m % p.mc == 0) return false;
+  const long long tail_panels = gp_ceil_div(chunk_cols(p, p.nchunks - 1), BC);
+  return (long long)p.batch * tail_panels * ((p.NI + 1) / 2) < trmm_slots();
 }
 
-// TRMM of chunks ch0 .. ch1 (consecutive; each chunk's cross-covariance `slab` doubles after the
-// one before, its partial sums `pslab` after) in one launch.
-hipError_t trmm_launch(const Plan& p, int ch0, int ch1, const double* kt, long long slab,
-                       double* part, long long pslab, const double* z, long long zld,
-                       const LinvRef& L, int m, int batch, hipStream_t stream) {
-  const int c1 = ch1 * p.mc;
-  const int mv1 = (m - c1 < p.mc) ? (m - c1) : p.mc;
+// TRMM of chunks ch0 .. ch1 (consecutive) in one launch.  Chunk ch0's cross-covariance and
+// partial sums are the workspace's slabs number `slab0`, the later chunks' the slabs after.
+hipError_t trmm_launch(const Plan& p, const WS& w, int slab0, int ch0, int ch1,
+                       const SolveSide& s, hipStream_t stream) {
   TrmmArgs a;
-  a.Linv = L.p;
-  a.sL = L.stride;
-  a.Kt2 = kt;
+  a.Linv = s.L.p;
+  a.sL = s.L.stride;
+  a.Kt2 = w.kt + slab0 * p.slab_elems;
   a.sK = (long long)p.mc * p.npad;
-  a.slab = slab;
-  a.z = z;
-  a.zld = zld;
-  a.part = part;
-  a.pslab = pslab;
-  a.ld = L.ld;
+  a.slab = p.slab_elems;
+  a.z = s.z;
+  a.zld = s.zld;
+  a.part = w.part + slab0 * p.part_elems;
+  a.pslab = p.part_elems;
+  a.ld = s.L.ld;
   a.mc = p.mc;
   a.NCc = p.NC;
-  a.NCt = (ch1 - ch0) * p.NC + gp_ceil_div(mv1, BC);
+  a.NCt = (ch1 - ch0) * p.NC + gp_ceil_div(chunk_cols(p, ch1), BC);
   a.npad = p.npad;
   a.NI = p.NI;
-  trmm_sched(a, batch, trmm_slots());
+  trmm_sched(a, p.batch, trmm_slots());
   const long long blocks = (long long)a.Gp * ((p.NI + 1) / 2) + (long long)a.Qc * p.NI;
-  if (L.packed)
-    hipLaunchKernelGGL(trmm_pair_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(trmm_pair_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  const auto kern = s.L.packed ? trmm_pair_kernel<true> : trmm_pair_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// mean / var of test points [j0, j0 + mv) from the partial sums (finalize_kernel; j0's chunk in
+// the workspace's first slab).
+hipError_t finalize(const Plan& p, const WS& w, int j0, int mv, const SolveSide& s,
+                    hipStream_t stream) {
+  hipLaunchKernelGGL(finalize_kernel, dim3(gp_ceil_div(mv, 256), p.batch), dim3(256), 0, stream,
+                     w.part, p.NI, p.mc, p.part_elems, j0, mv, s.s_pred, s.mean, s.var, s.ldo);
   return hipGetLastError();
 }
 
 // The column-resident kernel (trmm_res_kernel) serves every npad <= 512 prediction, with the
-// cross-covariance fused in when d <= 8 (res_fused) and from a materialised chunk otherwise.
+// cross-covariance fused in when d <= 8 and from a materialised chunk otherwise (pick_path).
 // gp_set_predict_path (A/B hook): 1 forces the cross-covariance + pair-TRMM path, 2 the
 // column-resident kernel from materialised chunks for every d.
 std::atomic<int> g_predict_path{0};
-bool res_eligible(int npad) {
-  return g_predict_path.load(std::memory_order_relaxed) != 1 && npad <= kResMaxPad;
-}
-bool res_fused(int d) { return g_predict_path.load(std::memory_order_relaxed) != 2 && d <= kResD; }
 
-// mean / var of test points [j0, j0 + mv) of every problem in one launch (problem-major blocks).
-hipError_t res_launch(int npad, const LinvRef& L, int n, int d, const double* X, int ldx,
-                      const double* Xs, int ldxs, int j0, int mv, const double* beta,
-                      int ldbeta, const double* s, const double* s_pred, const double* z,
-                      long long zld, double* mean, double* var, int ldo, int batch,
-                      const double* kt, long long sK, int mc, hipStream_t st) {
-  ResArgs a;
-  a.Linv = L.p;
-  a.sL = L.stride;
-  a.ld = L.ld;
-  a.n = n;
-  a.d = d;
-  a.mv = mv;
-  a.npanel = gp_ceil_div(mv, kResCols);
-  a.batch = batch;
-  a.X = X;
-  a.ldx = ldx;
-  a.Xs = Xs + (long long)j0 * ldxs;
-  a.ldxs = ldxs;
-  a.beta = beta;
-  a.ldbeta = ldbeta;
-  a.s = s;
-  a.s_pred = s_pred;
-  a.z = z;
-  a.zld = zld;
-  a.mean = mean + j0;
-  a.var = var + j0;
-  a.ldo = ldo;
-  a.kt = kt;
-  a.sK = sK;
-  a.mc = mc;
-  const long long total = (long long)batch * a.npanel;
-#define GP_RES_K(PK, RT, SL)                                                               \
-  hipLaunchKernelGGL((trmm_res_kernel<PK, RT, SL>), dim3((unsigned)total),                  \
-                     dim3(64 * res_waves(RT)), \
-                     0, st, a)
-#define GP_RES(RT)                                                            \
-  do {                                                                        \
-    if (kt) {                                                                 \
-      if (L.packed) GP_RES_K(true, RT, true); else GP_RES_K(false, RT, true); \
-    } else {                                                                  \
-      if (L.packed) GP_RES_K(true, RT, false); else GP_RES_K(false, RT, false); \
-    }                                                                         \
-  } while (0)
-  switch (npad / 128) {
-    case 1: GP_RES(1); break;
-    case 2: GP_RES(2); break;
-    case 3: GP_RES(3); break;
-    case 4: GP_RES(4); break;
+enum class Path {
+  PairTrmm,   // cross-covariance chunks + trmm_pair_kernel + finalize
+  ResFused,   // trmm_res_kernel producing K* itself
+  ResSlabs    // trmm_res_kernel reading materialised cross-covariance chunks
+};
+
+// The one decision about the path.  `materialised`: K* already sits in the workspace's slabs
+// (gp_predict_solve), so it is never produced again.
+Path pick_path(int npad, int d, bool materialised) {
+  const int forced = g_predict_path.load(std::memory_order_relaxed);
+  if (forced == 1 || npad > kResMaxPad) return Path::PairTrmm;
+  return (!materialised && forced != 2 && d <= kResD) ? Path::ResFused : Path::ResSlabs;
+}
+
+using ResKernel = void (*)(ResArgs);
+template <int RT>
+ResKernel res_kernel(bool packed, bool slab) {
+  if (slab) return packed ? trmm_res_kernel<true, RT, true> : trmm_res_kernel<false, RT, true>;
+  return packed ? trmm_res_kernel<true, RT, false> : trmm_res_kernel<false, RT, false>;
+}
+
+// mean / var of chunk ch's test points of every problem in one launch (problem-major blocks);
+// K* from kt (the chunk's cross-covariance) or, kt null, produced from c by the kernel.
+hipError_t res_launch(const Plan& p, int ch, const CrossSide* c, const SolveSide& s,
+                      const double* kt, hipStream_t st) {
+  const bool packed = s.L.packed, slab = kt != nullptr;
+  ResKernel kern;
+  switch (p.npad / 128) {
+    case 1: kern = res_kernel<1>(packed, slab); break;
+    case 2: kern = res_kernel<2>(packed, slab); break;
+    case 3: kern = res_kernel<3>(packed, slab); break;
+    case 4: kern = res_kernel<4>(packed, slab); break;
     default: return hipErrorInvalidValue;
   }
-#undef GP_RES
-#undef GP_RES_K
+  const long long j0 = (long long)ch * p.mc;
+  const CrossSide none{};
+  const CrossSide& x = c ? *c : none;
+  ResArgs a;
+  a.Linv = s.L.p;
+  a.sL = s.L.stride;
+  a.ld = s.L.ld;
+  a.n = p.n;
+  a.d = x.d;
+  a.mv = chunk_cols(p, ch);
+  a.npanel = gp_ceil_div(a.mv, kResCols);
+  a.batch = p.batch;
+  a.X = x.X;
+  a.ldx = x.ldx;
+  a.Xs = x.Xs + j0 * x.ldxs;
+  a.ldxs = x.ldxs;
+  a.beta = x.beta;
+  a.ldbeta = x.ldbeta;
+  a.s = x.s;
+  a.s_pred = s.s_pred;
+  a.z = s.z;
+  a.zld = s.zld;
+  a.mean = s.mean + j0;
+  a.var = s.var + j0;
+  a.ldo = s.ldo;
+  a.kt = kt;
+  a.sK = (long long)p.mc * p.npad;
+  a.mc = p.mc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long long)p.batch * a.npanel)),
+                     dim3(64 * kResWaves), 0, st, a);
   return hipGetLastError();
 }
 
 // trmm_res_kernel over all m test points, one launch per plan chunk (another stream's kernels
 // can interleave between launches, as with the TRMM chunks).  K* source: fused (d <= 8), the
-// prepared slabs of gp_predict_cross, or each chunk's cross-covariance built into slab 0 just
-// before its launch.
-enum class ResSrc { Fused, Prepared, Serial };
-
-hipError_t res_all(const Plan& p, const WS& w, ResSrc src, const LinvRef& L, int n, int m, int d,
-                   const double* X, int ldx, const double* Xs, int ldxs, const double* beta,
-                   int ldbeta, const double* s, const double* s_pred, const double* z,
-                   long long zld, double* mean, double* var, int ldo, int batch,
+// prepared slabs of gp_predict_cross (no cross-covariance side), or each chunk's
+// cross-covariance built into slab 0 just before its launch.
+hipError_t res_all(const Plan& p, const WS& w, Path path, const CrossSide* c, const SolveSide& s,
                    hipStream_t st) {
-  const bool one = src != ResSrc::Serial;    // one timing pair around all launches
-  if (one) gpfit_prof_begin_n(GP_PROF_TRMM, st, p.nchunks);
+  const bool slabs = path == Path::ResSlabs, serial = slabs && c;
+  if (!serial) gpfit_prof_begin_n(GP_PROF_TRMM, st, p.nchunks);   // one timing pair for all
   for (int ch = 0; ch < p.nchunks; ++ch) {
-    const int j0 = ch * p.mc;
-    const int mv = (m - j0 < p.mc) ? (m - j0) : p.mc;
-    const double* kt = nullptr;
     hipError_t e;
-    if (src == ResSrc::Prepared) {
-      kt = w.kt + (long long)ch * p.slab_elems;
-    } else if (src == ResSrc::Serial) {
+    if (serial) {
       gpfit_prof_begin(GP_PROF_CROSS, st);
-      if ((e = cross_chunk(p, ch, w.kt, X, ldx, Xs, ldxs, n, m, d, beta, ldbeta, s, batch,
-                           st)) != hipSuccess)
-        return e;
+      if ((e = cross_chunk(p, ch, w.kt, *c, st)) != hipSuccess) return e;
       gpfit_prof_end(GP_PROF_CROSS, st);
-      kt = w.kt;
+      gpfit_prof_begin(GP_PROF_TRMM, st);
     }
-    if (!one) gpfit_prof_begin(GP_PROF_TRMM, st);
-    e = res_launch(p.npad, L, n, d, X, ldx, Xs, ldxs, j0, mv, beta, ldbeta, s, s_pred, z, zld,
-                   mean, var, ldo, batch, kt, (long long)p.mc * p.npad, p.mc, st);
-    if (e != hipSuccess) return e;
-    if (!one) gpfit_prof_end(GP_PROF_TRMM, st);
+    const double* kt = serial ? w.kt : slabs ? w.kt + (long long)ch * p.slab_elems : nullptr;
+    if ((e = res_launch(p, ch, c, s, kt, st)) != hipSuccess) return e;
+    if (serial) gpfit_prof_end(GP_PROF_TRMM, st);
   }
-  if (one) gpfit_prof_end(GP_PROF_TRMM, st);
+  if (!serial) gpfit_prof_end(GP_PROF_TRMM, st);
   return hipSuccess;
+}
+
+// The column-resident paths' whole prediction: z = L^-1 w (skipped when w_hat is null: the
+// caller gave z), then res_all.
+hipError_t res_predict(const Plan& p, const WS& w, Path path, const CrossSide* c,
+                       const SolveSide& s, const double* w_hat, int ldw, hipStream_t st) {
+  if (w_hat) {
+    const hipError_t e = trmv_pred(p, w, s.L, w_hat, ldw, st);
+    if (e != hipSuccess) return e;
+  }
+  return res_all(p, w, path, c, s, st);
 }
 
 // Every chunk's TRMM into its own slab, then one finalize over all m points.  With `ready`
@@ -1295,13 +1239,11 @@ hipError_t res_all(const Plan& p, const WS& w, ResSrc src, const LinvRef& L, int
 // Chunks from `late` on (gp_fit_predict with gp_ctx_set_aux_chunks) have no cross-covariance
 // yet: `cross(ch)` enqueues it on `stream` just before that chunk's TRMM.
 template <typename Cross>
-hipError_t solve_all(const Plan& p, const WS& w, const LinvRef& L, const double* z,
-                     long long zld, int m, const double* s_pred, double* mean, double* var,
-                     int ldo, int batch, hipStream_t stream, const hipEvent_t* ready, int late,
-                     Cross&& cross) {
+hipError_t solve_all(const Plan& p, const WS& w, const SolveSide& s, hipStream_t stream,
+                     const hipEvent_t* ready, int late, Cross&& cross) {
   hipError_t e;
   if (ready && late > 0 && (e = hipStreamWaitEvent(stream, ready[0], 0)) != hipSuccess) return e;
-  const bool merge = trmm_merge_last(p, m, batch);
+  const bool merge = trmm_merge_last(p);
   const int nlaunch = p.nchunks - (merge ? 1 : 0);
   // timing: one event pair spans the back-to-back TRMM launches (an event record between
   // launches costs a few us of stream time each); gp_profile_read reports it per launch.
@@ -1325,16 +1267,12 @@ hipError_t solve_all(const Plan& p, const WS& w, const LinvRef& L, const double*
       }
     }
     if (split) gpfit_prof_begin(GP_PROF_TRMM, stream);
-    e = trmm_launch(p, ch, ch1, w.kt + (long long)ch * p.slab_elems, p.slab_elems,
-                    w.part + ch * p.part_elems, p.part_elems, z, zld, L, m, batch, stream);
-    if (e != hipSuccess) return e;
+    if ((e = trmm_launch(p, w, ch, ch, ch1, s, stream)) != hipSuccess) return e;
     if (split) gpfit_prof_end(GP_PROF_TRMM, stream);
     ch = ch1 + 1;
   }
   if (!split) gpfit_prof_end(GP_PROF_TRMM, stream);
-  hipLaunchKernelGGL(finalize_kernel, dim3(gp_ceil_div(m, 256), batch), dim3(256), 0, stream,
-                     w.part, p.NI, p.mc, p.part_elems, 0, m, s_pred, mean, var, ldo);
-  return hipGetLastError();
+  return finalize(p, w, 0, p.m, s, stream);
 }
 
 }  // namespace
@@ -1361,41 +1299,34 @@ extern "C" int gp_predict_ex(const double* Linv, int ldinv, long long strideInv,
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
   const WS w = carve(p, ws);
-  const LinvRef L{Linv, ldinv, strideInv, packed};
-  const double* zz = z ? z : w.z;
-  const long long zld = z ? ldz : p.npad;
-  hipError_t e;
-#define GP_CK(x) do { e = (x); if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e; } while (0)
-  if (!z) GP_CK(trmv_pred(p.npad, w.zp, L, w_hat, ldw, n, batch, w.z, p.npad, stream));
-  if (res_eligible(p.npad)) {
-    GP_CK(res_all(p, w, res_fused(d) ? ResSrc::Fused : ResSrc::Serial, L, n, m, d, X, ldx, Xs,
-                  ldxs, beta, ldbeta, s, s_pred, zz, zld, mean, var, ldo, batch, stream));
+  const CrossSide c{X, ldx, Xs, ldxs, d, beta, ldbeta, s};
+  const SolveSide sv{{Linv, ldinv, strideInv, packed}, s_pred, z ? z : w.z,
+                     z ? ldz : p.npad, mean, var, ldo};
+  const double* w_in = z ? nullptr : w_hat;   // with z given, no trmv
+  const Path path = pick_path(p.npad, d, false);
+  if (path != Path::PairTrmm) {
+    GP_CK(res_predict(p, w, path, &c, sv, w_in, ldw, stream));
     return 0;
   }
+  if (w_in) GP_CK(trmv_pred(p, w, sv.L, w_in, ldw, stream));
   // chunk by chunk: cross-covariance, TRMM, mean / var, reusing one slab -- except that a
   // merged last chunk (trmm_merge_last) has its own second slab, and its TRMM and finalize
   // cover the chunk before it too
-  const bool merge = trmm_merge_last(p, m, batch);
+  const bool merge = trmm_merge_last(p);
   for (int ch = 0; ch < p.nchunks; ++ch) {
     const bool held = merge && ch == p.nchunks - 2;   // TRMM deferred to the merged launch
     const int sl = (merge && ch == p.nchunks - 1) ? 1 : 0;
     gpfit_prof_begin(GP_PROF_CROSS, stream);
-    GP_CK(cross_chunk(p, ch, w.kt + sl * p.slab_elems, X, ldx, Xs, ldxs, n, m, d, beta, ldbeta,
-                      s, batch, stream));
+    GP_CK(cross_chunk(p, ch, w.kt + sl * p.slab_elems, c, stream));
     gpfit_prof_end(GP_PROF_CROSS, stream);
     if (held) continue;
-    const int ch0 = (merge && ch == p.nchunks - 1) ? ch - 1 : ch;
+    const int ch0 = ch - sl;
     gpfit_prof_begin(GP_PROF_TRMM, stream);
-    GP_CK(trmm_launch(p, ch0, ch, w.kt, p.slab_elems, w.part, p.part_elems, zz, zld, L, m, batch,
-                      stream));
+    GP_CK(trmm_launch(p, w, 0, ch0, ch, sv, stream));
     gpfit_prof_end(GP_PROF_TRMM, stream);
     const int j0 = ch0 * p.mc;
-    const int mv = (m - j0 < (ch - ch0 + 1) * p.mc) ? m - j0 : (ch - ch0 + 1) * p.mc;
-    hipLaunchKernelGGL(finalize_kernel, dim3(gp_ceil_div(mv, 256), batch), dim3(256), 0, stream,
-                       w.part, p.NI, p.mc, p.part_elems, j0, mv, s_pred, mean, var, ldo);
-    GP_CK(hipGetLastError());
+    GP_CK(finalize(p, w, j0, min(m - j0, (ch - ch0 + 1) * p.mc), sv, stream));
   }
-#undef GP_CK
   return 0;
 }
 
@@ -1416,31 +1347,30 @@ extern "C" int gp_predict(const double* Linv, int ldinv, long long strideInv, co
 extern "C" long long gp_predict_z_ws_bytes(int n, int batch) {
   if (n <= 0 || batch <= 0) return 0;
   const long long npad = gp_padded_n(n);
-  return ((8LL * batch * gp_ceil_div(npad, kZS) * npad + 255) / 256) * 256;
+  return align256(8LL * batch * gp_ceil_div(npad, kZS) * npad);
 }
 
 extern "C" int gp_predict_z(const double* Linv, int ldinv, long long strideInv, int layout,
                             int n, const double* w_hat, int ldw, double* z, long long ldz,
                             int batch, void* ws, long long ws_bytes, hipStream_t stream) {
-  if (!Linv || (reinterpret_cast<uintptr_t>(Linv) & 15)) return -1;
-  if (layout != GPFIT_LINV_PADDED && layout != GPFIT_LINV_PACKED) return -4;
   const bool packed = layout == GPFIT_LINV_PACKED;
+  // L^-1's pointer is reported before the layout and n, its leading dimension and stride after
+  const int lrc = check_linv(Linv, ldinv, strideInv, n, batch, packed, 0);
+  if (lrc == -1) return -1;
+  if (layout != GPFIT_LINV_PADDED && layout != GPFIT_LINV_PACKED) return -4;
   if (n < 0) return -5;
-  const int npad = gp_padded_n(n);
-  if (!packed && (ldinv < npad || (ldinv & 1))) return -2;
-  const long long per = packed ? linv_packed_elems(npad) : (long long)ldinv * npad;
-  if ((batch > 1 && strideInv < per) || (strideInv & 1)) return -3;
+  if (lrc) return lrc;
   if (!w_hat) return -6;
   if (ldw < n && batch > 1) return -7;
   if (!z) return -8;
-  if (ldz < npad && batch > 1) return -9;
+  if (ldz < gp_padded_n(n) && batch > 1) return -9;
   if (batch < 0) return -10;
   if (n == 0 || batch == 0) return 0;
   if (!ws) return -11;
   if (ws_bytes < gp_predict_z_ws_bytes(n, batch)) return -12;
-  const hipError_t e = trmv_pred(npad, static_cast<double*>(ws), LinvRef{Linv, ldinv, strideInv,
-                                 packed}, w_hat, ldw, n, batch, z, ldz, stream);
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(trmv_pred(LinvRef{Linv, ldinv, strideInv, packed}, n, batch, w_hat, ldw,
+                  static_cast<double*>(ws), z, ldz, stream));
+  return 0;
 }
 
 // The tile-packed layout (linv_col): gp_linv_packed_elems doubles per problem; pack from and
@@ -1516,13 +1446,11 @@ extern "C" int gp_predict_cross(const double* X, int ldx, const double* Xs, int 
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
   const WS w = carve(p, ws);
+  const CrossSide c{X, ldx, Xs, ldxs, d, beta, ldbeta, s};
   // one timing-event pair around all chunks (the stream runs nothing else in between)
   gpfit_prof_begin_n(GP_PROF_CROSS, stream, p.nchunks);
-  for (int ch = 0; ch < p.nchunks; ++ch) {
-    hipError_t e = cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, X, ldx, Xs, ldxs, n,
-                               m, d, beta, ldbeta, s, batch, stream);
-    if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
-  }
+  for (int ch = 0; ch < p.nchunks; ++ch)
+    GP_CK(cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, c, stream));
   gpfit_prof_end(GP_PROF_CROSS, stream);
   return 0;
 }
@@ -1542,18 +1470,14 @@ extern "C" int gp_predict_solve(const double* Linv, int ldinv, long long strideI
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
   const WS w = carve(p, ws);
-  hipError_t e;
-#define GP_CK(x) do { e = (x); if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e; } while (0)
-  const LinvRef L{Linv, ldinv, strideInv, false};
-  GP_CK(trmv_pred(p.npad, w.zp, L, w_hat, ldw, n, batch, w.z, p.npad, stream));
-  if (res_eligible(p.npad)) {
-    GP_CK(res_all(p, w, ResSrc::Prepared, L, n, m, 0, nullptr, 0, nullptr, 0, nullptr, 0,
-                  nullptr, s_pred, w.z, p.npad, mean, var, ldo, batch, stream));
+  const SolveSide sv{{Linv, ldinv, strideInv, false}, s_pred, w.z, p.npad, mean, var, ldo};
+  const Path path = pick_path(p.npad, 0, true);
+  if (path != Path::PairTrmm) {
+    GP_CK(res_predict(p, w, path, nullptr, sv, w_hat, ldw, stream));
     return 0;
   }
-  GP_CK(solve_all(p, w, L, w.z, p.npad, m, s_pred, mean, var, ldo, batch, stream, nullptr,
-                  p.nchunks, [](int) { return hipSuccess; }));
-#undef GP_CK
+  GP_CK(trmv_pred(p, w, sv.L, w_hat, ldw, stream));
+  GP_CK(solve_all(p, w, sv, stream, nullptr, p.nchunks, [](int) { return hipSuccess; }));
   return 0;
 }
 
@@ -1695,8 +1619,6 @@ extern "C" int gp_fit_predict(const double* X, int ldx, const double* Xs, int ld
   if (ws_bytes < p.bytes) return -22;
   const WS w = carve(p, ws);
   gp_ctx_s* S = static_cast<gp_ctx_s*>(ctx);
-  hipError_t e;
-#define GP_CK(x) do { e = (x); if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e; } while (0)
   if (S) {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != S->device) return -29;
@@ -1745,13 +1667,13 @@ extern "C" int gp_fit_predict(const double* X, int ldx, const double* Xs, int ld
                              w.pot, p.bytes - p.off_pot, fact, k_late > 0 ? k_late : -1,
                              (S && k_late > 0) ? S->e_late : nullptr, pre);
   if (rc) return rc;
-  const LinvRef L{Linv, ldinv, strideInv, false};
-  if (res_eligible(p.npad)) {
+  const CrossSide c{X, ldx, Xs, ldxs, d, beta, ldbeta, s};
+  const SolveSide sv{{Linv, ldinv, strideInv, false}, s_pred, w.z, p.npad, mean, var, ldo};
+  const Path path = pick_path(p.npad, d, false);
+  if (path != Path::PairTrmm) {
     // the cross-covariance is produced inside the prediction kernel (d <= 8; otherwise chunk
     // by chunk before each launch on pred): nothing forks onto aux
-    GP_CK(trmv_pred(p.npad, w.zp, L, w_hat, ldw, n, batch, w.z, p.npad, pred));
-    GP_CK(res_all(p, w, res_fused(d) ? ResSrc::Fused : ResSrc::Serial, L, n, m, d, X, ldx, Xs,
-                  ldxs, beta, ldbeta, s, s_pred, w.z, p.npad, mean, var, ldo, batch, pred));
+    GP_CK(res_predict(p, w, path, &c, sv, w_hat, ldw, pred));
     return 0;
   }
   if (S) GP_CK(hipStreamWaitEvent(aux, S->e_late, 0));
@@ -1764,8 +1686,7 @@ extern "C" int gp_fit_predict(const double* X, int ldx, const double* Xs, int ld
   // when the factorisation ends even if later chunks' cross-covariance is still running)
   if (n_aux > 0) gpfit_prof_begin_n(GP_PROF_CROSS, aux, n_aux);
   for (int ch = 0; ch < n_aux; ++ch) {
-    GP_CK(cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, X, ldx, Xs, ldxs, n, m, d,
-                      beta, ldbeta, s, batch, aux));
+    GP_CK(cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, c, aux));
     if (S && ch + 1 < n_aux) GP_CK(hipEventRecord(S->e_chunk[ch], aux));
   }
   if (n_aux > 0) gpfit_prof_end(GP_PROF_CROSS, aux);
@@ -1773,23 +1694,27 @@ extern "C" int gp_fit_predict(const double* X, int ldx, const double* Xs, int ld
   // the dispatcher interleaves another stream's kernels between launches, so a concurrent
   // factorisation is not starved behind a 25 ms grid (measured: 14 ms vs 3 ms per potrf).
   if (S && n_aux > 0) GP_CK(hipEventRecord(S->e_chunk[n_aux - 1], aux));   // after the end event
-  GP_CK(trmv_pred(p.npad, w.zp, L, w_hat, ldw, n, batch, w.z, p.npad, pred));
-  GP_CK(solve_all(p, w, L, w.z, p.npad, m, s_pred, mean, var, ldo, batch, pred,
-                  S ? S->e_chunk.data() : nullptr, n_aux, [&](int ch) {
-                    return cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, X, ldx, Xs,
-                                       ldxs, n, m, d, beta, ldbeta, s, batch, pred);
-                  }));
+  GP_CK(trmv_pred(p, w, sv.L, w_hat, ldw, pred));
+  GP_CK(solve_all(p, w, sv, pred, S ? S->e_chunk.data() : nullptr, n_aux, [&](int ch) {
+    return cross_chunk(p, ch, w.kt + (long long)ch * p.slab_elems, c, pred);
+  }));
   // (every chunk's cross-covariance on aux is joined by the TRMM that waits for its event)
-#undef GP_CK
   return 0;
 }
 
 // gp_predict from a Cholesky factor L (LAPACK layout): L^-1 by gp_trtri into the head of the
 // workspace, then gp_predict with the rest.
+namespace {
+// bytes of the padded L^-1 at the head of gp_predict_chol's workspace
+long long chol_head_bytes(int n, int batch) {
+  const long long npad = gp_padded_n(n);
+  return align256(8LL * npad * npad * batch);
+}
+}  // namespace
+
 extern "C" long long gp_predict_chol_ws_bytes(int n, int m, int batch, int m_chunk) {
   if (n <= 0 || m <= 0 || batch <= 0) return 0;
-  const long long npad = gp_padded_n(n);
-  return ((8LL * npad * npad * batch + 255) / 256) * 256 + make_plan(n, m, batch, m_chunk).bytes;
+  return chol_head_bytes(n, batch) + make_plan(n, m, batch, m_chunk).bytes;
 }
 
 extern "C" int gp_predict_chol(const double* L, int ldl, long long strideL, const double* X,
@@ -1807,8 +1732,7 @@ extern "C" int gp_predict_chol(const double* L, int ldl, long long strideL, cons
   if (m_chunk < 0) return -24;
   if (!ws) return -22;
   if (ws_bytes < gp_predict_chol_ws_bytes(n, m, batch, m_chunk)) return -23;
-  const long long npad = gp_padded_n(n);
-  const long long head = ((8LL * npad * npad * batch + 255) / 256) * 256;
+  const long long npad = gp_padded_n(n), head = chol_head_bytes(n, batch);
   double* Linv = static_cast<double*>(ws);
   rc = gp_trtri(L, n, ldl, strideL, Linv, (int)npad, npad * npad, batch, info, stream);
   if (rc) return rc;

@@ -150,6 +150,193 @@ def test_new_entry_points_validate(lib):
     assert lib.gp_ctx_set_aux_chunks(dummy, -5) == -2      # rejected before the handle is read
 
 
+# Return codes of the prediction entry points.  Each base argument list is valid except for a
+# null workspace, so the call returns that code and never reaches a launch; every row breaks
+# the named arguments of the base list and gives the code the library must return.  Rows with
+# two faults pin the order in which errors are reported.
+_P = 16          # a non-null, 16-B aligned address (never dereferenced)
+_N, _M, _NPAD = 100, 10, 128
+_CROSS = dict(X=_P, ldx=2, Xs=_P, ldxs=2, n=_N, m=_M, d=2, beta=_P, ldbeta=2, s=_P)
+_LINV = dict(Linv=_P, ldinv=_NPAD, strideInv=_NPAD * _NPAD)
+_OUT = dict(s_pred=_P, w_hat=_P, ldw=_N, mean=_P, var=_P, ldo=_M)
+_WS = dict(batch=2, ws=None, ws_bytes=1 << 40, m_chunk=0)
+_PACKED_ELEMS = _NPAD * _NPAD - 128 * 8 * 7      # gp_linv_packed_elems(100)
+
+
+def _rows_cross(c):
+    """check_common's codes; c maps the shared names to this entry point's codes."""
+    return [(dict(X=None), c["X"]), (dict(ldx=1), c["ldx"]), (dict(Xs=None), c["Xs"]),
+            (dict(ldxs=1), c["ldxs"]), (dict(n=-1), c["n"]), (dict(m=-1), c["m"]),
+            (dict(d=0), c["d"]), (dict(d=33, ldx=33, ldxs=33, ldbeta=33), c["d"]),
+            (dict(beta=None), c["beta"]), (dict(ldbeta=1), c["ldbeta"]),
+            (dict(ldbeta=1, batch=1), c["ws"]),             # ldbeta is a batch stride
+            (dict(s=None), c["s"]), (dict(batch=-1), c["batch"]),
+            (dict(X=None, ldx=1), c["X"]), (dict(s=None, batch=-1), c["s"]),
+            (dict(n=0), 0), (dict(m=0), 0), (dict(batch=0), 0)]
+
+
+def _rows_linv(c):
+    """The L^-1 pointer / leading dimension / stride codes (padded layout)."""
+    return [(dict(Linv=None), c["Linv"]), (dict(Linv=8), c["Linv"]),
+            (dict(ldinv=64), c["ldinv"]), (dict(ldinv=_NPAD + 1), c["ldinv"]),
+            (dict(strideInv=_NPAD * _NPAD - 2), c["strideInv"]),
+            (dict(strideInv=_NPAD * _NPAD + 1), c["strideInv"]),
+            (dict(strideInv=0, batch=1), c["ws"]),          # one problem: no stride to check
+            (dict(strideInv=1, batch=1), c["strideInv"]),   # ... but it must stay even
+            (dict(Linv=None, ldinv=64), c["Linv"]),
+            (dict(ldinv=64, strideInv=1), c["ldinv"])]
+
+
+def _rows_out(c):
+    return [(dict(s_pred=None), c["s_pred"]), (dict(w_hat=None), c["w_hat"]),
+            (dict(ldw=_N - 1), c["ldw"]), (dict(ldw=0, batch=1), c["ws"]),
+            (dict(mean=None), c["mean"]), (dict(var=None), c["var"]),
+            (dict(ldo=_M - 1), c["ldo"]), (dict(ldo=0, batch=1), c["ws"]),
+            (dict(s_pred=None, var=None), c["s_pred"]), (dict(mean=None, ldo=0), c["mean"])]
+
+
+_SOLVE_CODES = dict(Linv=-1, ldinv=-2, strideInv=-3, s_pred=-14, w_hat=-15, ldw=-16, mean=-17,
+                    var=-18, ldo=-19)
+_COMMON_CODES = dict(X=-4, ldx=-5, Xs=-6, ldxs=-7, n=-8, m=-9, d=-10, beta=-11, ldbeta=-12,
+                     s=-13, batch=-20)
+
+
+def _predict_ex_table():
+    c = dict(_COMMON_CODES, **_SOLVE_CODES, ws=-21)
+    order = ["Linv", "ldinv", "strideInv", "X", "ldx", "Xs", "ldxs", "n", "m", "d", "beta",
+             "ldbeta", "s", "s_pred", "w_hat", "ldw", "mean", "var", "ldo", "batch", "ws",
+             "ws_bytes", "m_chunk", "layout", "z", "ldz", "stream"]
+    base = dict(_LINV, **_CROSS, **_OUT, **_WS, layout=0, z=None, ldz=0, stream=None)
+    rows = _rows_cross(c) + _rows_linv(c) + _rows_out(c) + [
+        (dict(layout=2), -24), (dict(layout=-1), -24),
+        (dict(layout=2, Linv=None), -24),                   # layout before L^-1
+        (dict(layout=2, X=None), -24),
+        (dict(Linv=None, X=None), -4),                      # the design before L^-1
+        (dict(X=None, mean=None), -4),
+        (dict(layout=1, ldinv=0), -21),                     # packed: ldinv ignored
+        (dict(layout=1, strideInv=_PACKED_ELEMS), -21),
+        (dict(layout=1, strideInv=_PACKED_ELEMS - 2), -3),
+        (dict(layout=1, Linv=8), -1),
+        (dict(z=_P, ldz=_NPAD), -21),
+        (dict(z=_P, ldz=_NPAD, w_hat=None), -21),           # with z, w_hat is not read
+        (dict(z=_P, ldz=_NPAD - 1), -26),
+        (dict(z=_P, ldz=0, batch=1), -21),
+        (dict(z=_P, ldz=_NPAD - 1, mean=None), -17),        # outputs before ldz
+        (dict(z=_P, ldz=-1, n=0), -26),                     # ... and ldz before the no-op
+        (dict(n=0, ldinv=0), -2), (dict(n=0, ldinv=2, strideInv=0), 0),
+        (dict(m_chunk=-1), -23),                            # m_chunk before the workspace
+        (dict(m_chunk=-1, n=0), 0),                         # ... and after the no-op
+        (dict(m_chunk=-1, ldo=0), -19),
+        (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
+    return "gp_predict_ex", order, base, -21, rows
+
+
+def _predict_cross_table():
+    c = dict(_COMMON_CODES, ws=-21)
+    order = ["X", "ldx", "Xs", "ldxs", "n", "m", "d", "beta", "ldbeta", "s", "batch", "ws",
+             "ws_bytes", "m_chunk", "stream"]
+    base = dict(_CROSS, **_WS, stream=None)
+    rows = _rows_cross(c) + [
+        (dict(m_chunk=-1), -23), (dict(m_chunk=-1, m=0), 0), (dict(m_chunk=-1, s=None), -13),
+        (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
+    return "gp_predict_cross", order, base, -21, rows
+
+
+def _predict_solve_table():
+    c = dict(_SOLVE_CODES, ws=-21)
+    order = ["Linv", "ldinv", "strideInv", "n", "m", "s_pred", "w_hat", "ldw", "mean", "var",
+             "ldo", "batch", "ws", "ws_bytes", "m_chunk", "stream"]
+    base = dict(_LINV, n=_N, m=_M, **_OUT, **_WS, stream=None)
+    rows = _rows_linv(c) + _rows_out(c) + [
+        (dict(n=-1), -4), (dict(m=-1), -5), (dict(batch=-1), -12),
+        (dict(n=-1, Linv=None), -4), (dict(batch=-1, Linv=None), -12),   # sizes before L^-1
+        (dict(n=-1, m=-1), -4), (dict(m=-1, batch=-1), -5),
+        (dict(n=0), 0), (dict(m=0), 0), (dict(batch=0), 0),
+        (dict(n=0, ldinv=0), -2), (dict(n=0, mean=None), -17),
+        (dict(m_chunk=-1), -23), (dict(m_chunk=-1, m=0), 0), (dict(m_chunk=-1, var=None), -18),
+        (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
+    return "gp_predict_solve", order, base, -21, rows
+
+
+def _predict_z_table():
+    order = ["Linv", "ldinv", "strideInv", "layout", "n", "w_hat", "ldw", "z", "ldz", "batch",
+             "ws", "ws_bytes", "stream"]
+    base = dict(_LINV, layout=0, n=_N, w_hat=_P, ldw=_N, z=_P, ldz=_NPAD, batch=2, ws=None,
+                ws_bytes=1 << 40, stream=None)
+    c = dict(Linv=-1, ldinv=-2, strideInv=-3, ws=-11)
+    rows = _rows_linv(c) + [
+        (dict(layout=2), -4), (dict(n=-1), -5), (dict(w_hat=None), -6), (dict(ldw=_N - 1), -7),
+        (dict(ldw=0, batch=1), -11), (dict(z=None), -8), (dict(ldz=_NPAD - 1), -9),
+        (dict(ldz=0, batch=1), -11), (dict(batch=-1), -10),
+        (dict(Linv=None, layout=2), -1),                    # L^-1's pointer before the layout
+        (dict(Linv=8, n=-1), -1),
+        (dict(layout=2, ldinv=64), -4), (dict(layout=2, n=-1), -4),
+        (dict(n=-1, ldinv=-1), -5), (dict(n=-1, strideInv=1), -5),   # n before ld / stride
+        (dict(ldinv=64, w_hat=None), -2), (dict(strideInv=1, w_hat=None), -3),
+        (dict(w_hat=None, z=None), -6), (dict(z=None, batch=-1), -8),
+        (dict(layout=1, ldinv=0), -11), (dict(layout=1, strideInv=_PACKED_ELEMS), -11),
+        (dict(layout=1, strideInv=_PACKED_ELEMS - 2), -3),
+        (dict(n=0), 0), (dict(batch=0), 0), (dict(n=0, ldinv=0), 0),
+        (dict(n=0, batch=-1), -10),
+        (dict(ws=256, ws_bytes=16), -12)]
+    return "gp_predict_z", order, base, -11, rows
+
+
+def _predict_chol_table():
+    c = dict(_COMMON_CODES, ws=-22)
+    order = ["L", "ldl", "strideL", "X", "ldx", "Xs", "ldxs", "n", "m", "d", "beta", "ldbeta",
+             "s", "s_pred", "w_hat", "ldw", "mean", "var", "ldo", "batch", "info", "ws",
+             "ws_bytes", "m_chunk", "stream"]
+    base = dict(L=_P, ldl=_N, strideL=_N * _N, **_CROSS, **_OUT, **_WS, info=None, stream=None)
+    rows = _rows_cross(c) + [
+        (dict(L=None), -1), (dict(ldl=_N - 1), -2), (dict(strideL=_N * _N - 1), -3),
+        (dict(strideL=0, batch=1), -22),
+        (dict(L=None, X=None), -1), (dict(ldl=_N - 1, X=None), -2), (dict(strideL=0, X=None), -3),
+        (dict(m_chunk=-1), -24),                            # m_chunk before the workspace
+        (dict(m_chunk=-1, n=0), 0),
+        (dict(ws=256, ws_bytes=16), -23), (dict(ws=256, ws_bytes=16, m_chunk=-1), -24)]
+    return "gp_predict_chol", order, base, -22, rows
+
+
+def _fit_predict_table():
+    c = dict(_COMMON_CODES, **_SOLVE_CODES, ws=-21)
+    order = ["X", "ldx", "Xs", "ldxs", "n", "m", "d", "beta", "ldbeta", "s", "delta", "s_pred",
+             "w_hat", "ldw", "G", "ldg", "strideG", "Linv", "ldinv", "strideInv", "info",
+             "logdet", "mean", "var", "ldo", "batch", "ws", "ws_bytes", "m_chunk", "ctx",
+             "stream"]
+    base = dict(_CROSS, **_LINV, **_OUT, **_WS, delta=_P, G=_P, ldg=_N, strideG=_N * _N,
+                info=None, logdet=None, ctx=None, stream=None)
+    rows = _rows_cross(c) + _rows_linv(c) + _rows_out(c) + [
+        (dict(delta=None), -24), (dict(G=None), -25), (dict(ldg=_N - 1), -26),
+        (dict(strideG=_N * _N - 1), -26), (dict(strideG=0, batch=1), -21),
+        (dict(Linv=None, X=None), -4), (dict(delta=None, ldo=0), -19),
+        (dict(delta=None, G=None), -24), (dict(G=None, n=0), -25),
+        (dict(m_chunk=-1), -23), (dict(m_chunk=-1, n=0), 0), (dict(m_chunk=-1, ldg=0), -26),
+        (dict(ws=16), -21),                                 # workspace not 256-B aligned
+        (dict(ws=256, ws_bytes=16), -22), (dict(ws=16, ws_bytes=16), -21),
+        (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
+    return "gp_fit_predict", order, base, -21, rows
+
+
+@pytest.mark.parametrize("table", [_predict_ex_table, _predict_cross_table,
+                                   _predict_solve_table, _predict_z_table,
+                                   _predict_chol_table, _fit_predict_table],
+                         ids=lambda t: t.__name__.strip("_"))
+def test_prediction_return_codes(lib, table):
+    """gp_predict_ex / _cross / _solve / _z / _chol and gp_fit_predict: which argument is
+    reported, and in which order, before anything is enqueued."""
+    name, order, base, base_rc, rows = table()
+    assert sorted(order) == sorted(base), name
+    fn = getattr(lib, name)
+    assert fn(*[base[k] for k in order]) == base_rc
+    got = []
+    for change, _ in rows:
+        assert set(change) <= set(base), (name, change)
+        got.append(fn(*[dict(base, **change)[k] for k in order]))
+    assert got == [rc for _, rc in rows], [
+        (change, want, g) for (change, want), g in zip(rows, got) if g != want]
+
+
 def test_mcmc_group_step_validates(lib):
     """gp_mcmc_group_step: both groups' arguments are checked before the launch (the second
     group's prep codes shifted by -10)."""

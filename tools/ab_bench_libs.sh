@@ -1,6 +1,7 @@
 #!/bin/bash
 # Same-box A/B of whole library builds on the C3 and C4 benches: each build in turn is copied
-# over gladsgp_amd/libgpfit.so, two interleaved rounds.
+# over gladsgp_amd/libgpfit.so, AB_ROUNDS (default 2) interleaved rounds of AB_WORKLOADS
+# (default "c3 c4").
 #   tools/ab_bench_libs.sh TAG lib1.so lib2.so ...   -> gpurun_out/TAG.log
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
@@ -8,7 +9,7 @@ TAG=$1; shift
 mkdir -p gpurun_out
 cp gladsgp_amd/libgpfit.so gpurun_out/.libgpfit_keep.so
 : > gpurun_out/$TAG.log
-for rep in 1 2; do
+for rep in $(seq 1 "${AB_ROUNDS:-2}"); do
   for lib in "$@"; do
     cp "$lib" gladsgp_amd/libgpfit.so
     for wl in ${AB_WORKLOADS:-c3 c4}; do
