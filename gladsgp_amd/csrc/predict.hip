@@ -1298,6 +1298,7 @@ extern "C" int gp_predict_ex(const double* Linv, int ldinv, long long strideInv,
   const Plan p = make_plan(n, m, batch, m_chunk);
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return -21;   // 256-B aligned (include/gpfit.h)
   const WS w = carve(p, ws);
   const CrossSide c{X, ldx, Xs, ldxs, d, beta, ldbeta, s};
   const SolveSide sv{{Linv, ldinv, strideInv, packed}, s_pred, z ? z : w.z,
@@ -1368,6 +1369,7 @@ extern "C" int gp_predict_z(const double* Linv, int ldinv, long long strideInv, 
   if (n == 0 || batch == 0) return 0;
   if (!ws) return -11;
   if (ws_bytes < gp_predict_z_ws_bytes(n, batch)) return -12;
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return -11;   // 256-B aligned (include/gpfit.h)
   GP_CK(trmv_pred(LinvRef{Linv, ldinv, strideInv, packed}, n, batch, w_hat, ldw,
                   static_cast<double*>(ws), z, ldz, stream));
   return 0;
@@ -1445,6 +1447,7 @@ extern "C" int gp_predict_cross(const double* X, int ldx, const double* Xs, int 
   const Plan p = make_plan(n, m, batch, m_chunk, true);
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return -21;   // 256-B aligned (include/gpfit.h)
   const WS w = carve(p, ws);
   const CrossSide c{X, ldx, Xs, ldxs, d, beta, ldbeta, s};
   // one timing-event pair around all chunks (the stream runs nothing else in between)
@@ -1469,6 +1472,7 @@ extern "C" int gp_predict_solve(const double* Linv, int ldinv, long long strideI
   const Plan p = make_plan(n, m, batch, m_chunk, true);
   if (!ws) return -21;
   if (ws_bytes < p.bytes) return -22;
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return -21;   // 256-B aligned (include/gpfit.h)
   const WS w = carve(p, ws);
   const SolveSide sv{{Linv, ldinv, strideInv, false}, s_pred, w.z, p.npad, mean, var, ldo};
   const Path path = pick_path(p.npad, 0, true);
@@ -1732,6 +1736,7 @@ extern "C" int gp_predict_chol(const double* L, int ldl, long long strideL, cons
   if (m_chunk < 0) return -24;
   if (!ws) return -22;
   if (ws_bytes < gp_predict_chol_ws_bytes(n, m, batch, m_chunk)) return -23;
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return -22;   // 256-B aligned (include/gpfit.h)
   const long long npad = gp_padded_n(n), head = chol_head_bytes(n, batch);
   double* Linv = static_cast<double*>(ws);
   rc = gp_trtri(L, n, ldl, strideL, Linv, (int)npad, npad * npad, batch, info, stream);

@@ -22,6 +22,20 @@
  *  - `batch` independent problems share X / Xs; per-problem operands advance by the given
  *    stride (matrices), by ldbeta (beta rows), by 1 (s, delta, s_pred, info, logdet) and by
  *    ldw / ldo (w_hat, mean, var columns);
+ *  - layout contract: an operand may be a sub-view of a larger array.  Any naturally aligned
+ *    base (8 bytes for doubles, 4 for a float32 operand or output) and any leading dimension /
+ *    row stride / batch stride at or above the stated minimum are accepted, odd values included;
+ *    only the elements the function's comment names are read or written (never the rows between
+ *    the logical extent and ld, nor the gap between two problems), and the results do not depend
+ *    on the layout bit for bit: alignment only selects wider loads and stores where it allows
+ *    them ("Operand layouts and the branches they select").  The exceptions, each
+ *    reported by its argument number before anything is launched:
+ *      - the L^-1 the prediction READS (gp_predict, gp_predict_ex, gp_predict_z,
+ *        gp_predict_solve, gp_fit_predict's Linv) and both buffers of gp_pack_linv /
+ *        gp_unpack_linv: 16-byte aligned base, even ldinv, even strideInv (gp_potrf_inv,
+ *        gp_trtri, gp_trmv and gp_nll take any L^-1 layout);
+ *      - every workspace `ws`: 256-byte aligned (gp_dgemm / gp_gemm_ex's split-K scratch and
+ *        the `work` vectors of gp_nll / gp_mean_var: 8 bytes);
  *  - stream-ordered and asynchronous on `stream`; no host synchronisation, so calls can be
  *    captured into a hipGraph;
  *  - return 0 on success, -k when argument k is invalid (LAPACK style), or

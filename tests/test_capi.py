@@ -227,6 +227,7 @@ def _predict_ex_table():
         (dict(m_chunk=-1), -23),                            # m_chunk before the workspace
         (dict(m_chunk=-1, n=0), 0),                         # ... and after the no-op
         (dict(m_chunk=-1, ldo=0), -19),
+        (dict(ws=16), -21),                                 # workspace not 256-B aligned
         (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
     return "gp_predict_ex", order, base, -21, rows
 
@@ -238,6 +239,7 @@ def _predict_cross_table():
     base = dict(_CROSS, **_WS, stream=None)
     rows = _rows_cross(c) + [
         (dict(m_chunk=-1), -23), (dict(m_chunk=-1, m=0), 0), (dict(m_chunk=-1, s=None), -13),
+        (dict(ws=16), -21),
         (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
     return "gp_predict_cross", order, base, -21, rows
 
@@ -254,6 +256,7 @@ def _predict_solve_table():
         (dict(n=0), 0), (dict(m=0), 0), (dict(batch=0), 0),
         (dict(n=0, ldinv=0), -2), (dict(n=0, mean=None), -17),
         (dict(m_chunk=-1), -23), (dict(m_chunk=-1, m=0), 0), (dict(m_chunk=-1, var=None), -18),
+        (dict(ws=16), -21),
         (dict(ws=256, ws_bytes=16), -22), (dict(ws=256, ws_bytes=16, m_chunk=-1), -23)]
     return "gp_predict_solve", order, base, -21, rows
 
@@ -278,7 +281,7 @@ def _predict_z_table():
         (dict(layout=1, strideInv=_PACKED_ELEMS - 2), -3),
         (dict(n=0), 0), (dict(batch=0), 0), (dict(n=0, ldinv=0), 0),
         (dict(n=0, batch=-1), -10),
-        (dict(ws=256, ws_bytes=16), -12)]
+        (dict(ws=16), -11), (dict(ws=256, ws_bytes=16), -12)]
     return "gp_predict_z", order, base, -11, rows
 
 
@@ -294,6 +297,7 @@ def _predict_chol_table():
         (dict(L=None, X=None), -1), (dict(ldl=_N - 1, X=None), -2), (dict(strideL=0, X=None), -3),
         (dict(m_chunk=-1), -24),                            # m_chunk before the workspace
         (dict(m_chunk=-1, n=0), 0),
+        (dict(ws=16), -22),
         (dict(ws=256, ws_bytes=16), -23), (dict(ws=256, ws_bytes=16, m_chunk=-1), -24)]
     return "gp_predict_chol", order, base, -22, rows
 
@@ -335,6 +339,47 @@ def test_prediction_return_codes(lib, table):
         got.append(fn(*[dict(base, **change)[k] for k in order]))
     assert got == [rc for _, rc in rows], [
         (change, want, g) for (change, want), g in zip(rows, got) if g != want]
+
+
+def test_required_alignment_return_codes(lib):
+    """The operands whose alignment the header requires (include/gpfit.h, layout contract): a
+    16-B aligned L^-1 / packed P with an even ldinv and strideInv, a 256-B aligned workspace.
+    An 8-B-only base, an odd leading dimension and an odd stride each return the argument's
+    number before any launch (gp_predict_ex / _solve / _z and gp_fit_predict: _rows_linv)."""
+    p16, p8, ws256, ws16 = 16, 8, ctypes.c_void_p(256), ctypes.c_void_p(16)
+    order = ["Linv", "ldinv", "strideInv", "X", "ldx", "Xs", "ldxs", "n", "m", "d", "beta",
+             "ldbeta", "s", "s_pred", "w_hat", "ldw", "mean", "var", "ldo", "batch", "ws",
+             "ws_bytes", "m_chunk", "stream"]
+    base = dict(_LINV, **_CROSS, **_OUT, **_WS, stream=None)
+    rows = [(dict(), -21), (dict(Linv=p8), -1), (dict(ldinv=_NPAD + 1), -2),
+            (dict(strideInv=_NPAD * _NPAD + 1), -3), (dict(strideInv=1, batch=1), -3),
+            (dict(ldinv=_NPAD + 2, strideInv=(_NPAD + 2) * _NPAD), -21),   # even: accepted
+            (dict(ws=16), -21)]
+    for change, want in rows:
+        assert lib.gp_predict(*[dict(base, **change)[k] for k in order]) == want, change
+    # gp_pack_linv / gp_unpack_linv: both buffers 16-B aligned, ldinv even
+    assert lib.gp_pack_linv(p8, 100, 128, p16, None) == -1
+    assert lib.gp_pack_linv(p16, 100, 129, p16, None) == -3
+    assert lib.gp_pack_linv(p16, 100, 128, p8, None) == -4
+    assert lib.gp_unpack_linv(p8, 100, p16, 128, None) == -1
+    assert lib.gp_unpack_linv(p16, 100, p8, 128, None) == -3
+    assert lib.gp_unpack_linv(p16, 100, p16, 129, None) == -4
+    # workspaces: 256-B aligned
+    assert lib.gp_potrf_inv_ws(p16, 100, 100, 10000, p16, 128, 128 * 128, 1, None, None, ws16,
+                               1 << 30, None) == -11
+    assert lib.gp_potrf_ws(p16, 100, 100, 10000, 1, None, None, ws16, 1 << 30, None) == -8
+    assert lib.gp_predict_z(p16, 128, 128 * 128, 0, 100, p16, 100, p16, 128, 1, ws16, 1 << 30,
+                            None) == -11
+    chol = [p16, 100, 10000, p16, 2, p16, 2, 100, 10, 2, p16, 2, p16, p16, p16, 100, p16, p16,
+            10, 1, None, ws16, 1 << 40, 0, None]
+    assert lib.gp_predict_chol(*chol) == -22
+    chol[21] = ws256
+    chol[22] = 16
+    assert lib.gp_predict_chol(*chol) == -23
+    # the factor of gp_predict_chol / gp_trtri and the L^-1 of gp_trmv / gp_nll carry no
+    # alignment requirement: an 8-B-only base and odd ld pass validation (no-op sizes here)
+    assert lib.gp_trtri(p8, 0, 1, 1, p8, 1, 1, 1, None, None) == 0
+    assert lib.gp_trmv(p8, 129, 129 * 128 + 1, 0, p8, 1, p8, 1, 3, None) == 0
 
 
 def test_mcmc_group_step_validates(lib):
