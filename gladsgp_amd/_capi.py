@@ -115,6 +115,11 @@ SIGNATURES = {
     "gp_field_summary": (c_int, [c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_void_p, c_ll, c_int,
                                  c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
                                  c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
+    "gp_sobol_replicates": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_ll, c_int, c_int, ctypes.c_ulonglong,
+                                    ctypes.c_ulonglong, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_ll, c_void_p, c_void_p, c_ll, c_void_p]),
+    "gp_sobol_lds_points": (c_ll, [c_int]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

@@ -473,6 +473,44 @@ int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m
                      const double* mu, const double* err, double q_lo, double q_hi, void* mean,
                      void* lo, void* hi, long long ldo, int out_f32, hipStream_t stream);
 
+/* Saltelli estimators of the Sobol' sensitivity indices for R replicates of the design rows: the
+ * statistic that saltelli_sensitivity_indices / PCA_saltelli_sensitivity_indices evaluate once
+ * for the point estimate and then 9,999 times per scipy.stats.bootstrap call, plus N jackknife
+ * evaluations for BCa (src/utils.py:27-256, called from sensitivity_indices.py:96,214), here one
+ * asynchronous launch per set of replicates.  Operands are output-major: output j at design row k
+ * is fA[j*ldf + k], fB[j*ldf + k] and, with input i taken from A, fAB[i*strideAB + j*ldf + k]
+ * (ldf >= N, strideAB >= (p-1) ldf + N).  Replicate r uses the M = n_draw rows i_0 .. i_{M-1}:
+ *   GPFIT_SOBOL_IDENTITY   i_k = k                         (R = 1, n_draw = N: the point estimate)
+ *   GPFIT_SOBOL_INDEX      i_k = idx[r*ldi + k], ldi >= n_draw, clamped into [0, N)
+ *   GPFIT_SOBOL_PHILOX     i_k = (x N) >> 32, x = word k & 3 of Philox4x32-10 (gp_realize's) with
+ *                          key seed and counter (k >> 2, r, offset_lo, offset_hi)
+ *   GPFIT_SOBOL_JACKKNIFE  i_k = k + (k >= r)              (R = N, n_draw = N - 1: leave r out)
+ * the same rows for every output and input.  With a_k, b_k, c_k = fA, fB, fAB_i at row i_k:
+ *   mu = (sum a + sum b) / (2M),  var = (sum (a-mu)^2 + sum (b-mu)^2) / (2M)   (two-pass),
+ *   V = sum a (c - b) / M  (V < 0 -> 0 when clamp != 0, as the reference's bootstrap statistic
+ *   does and its point estimate does not),  E = sum (b - c)^2 / (2M),
+ *   first[r*ldr + j*d + i] = V / var,  total[r*ldr + j*d + i] = E / var,  ldr >= p d,
+ * and, when pcvar is given, the general indices of the whole field
+ *   gfirst[r*ldg + i] = sum_j pcvar[j] first[r, j, i] (increasing j), gtotal likewise, ldg >= d;
+ * pcvar, gfirst and gtotal are NULL together or not at all.  fp64 throughout, no atomics: equal
+ * inputs give equal bits, and so do two modes that select the same rows.  Allocates nothing and
+ * can be captured into a hipGraph.  2 <= N <= 2^20, 1 <= d <= GPFIT_MAX_DIM, p >= 1, R >= 0
+ * (R = 0: no launch); a violation returns its argument number (a mode's R / n_draw rule: -13 /
+ * -12; a NULL pointer: its own number) before any launch.  gp_sobol_lds_points(d): the largest N
+ * whose (d + 2) N working set the kernel keeps in LDS (0 for d out of range); above it the same
+ * kernel gathers from global memory. */
+#define GPFIT_SOBOL_IDENTITY 0
+#define GPFIT_SOBOL_INDEX 1
+#define GPFIT_SOBOL_PHILOX 2
+#define GPFIT_SOBOL_JACKKNIFE 3
+int gp_sobol_replicates(
+    const double* fA, const double* fB, const double* fAB, long long ldf, long long strideAB,
+    int N, int p, int d, int mode, const int* idx, long long ldi, int n_draw, int R,
+    unsigned long long seed, unsigned long long offset, const double* pcvar, int clamp,
+    double* first, double* total, long long ldr, double* gfirst, double* gtotal, long long ldg,
+    hipStream_t stream);
+long long gp_sobol_lds_points(int d);
+
 /* out[0] = mean(x), out[1] = var(x, ddof) of a length-N vector (two-pass, deterministic);
  * work holds 1024 doubles.  np.var of the PC truncation residual, src/model.py:222. */
 int gp_mean_var(const double* x, long long N, int ddof, double* out, double* work,
