@@ -120,6 +120,11 @@ SIGNATURES = {
                                     ctypes.c_ulonglong, c_void_p, c_int, c_void_p, c_void_p,
                                     c_ll, c_void_p, c_void_p, c_ll, c_void_p]),
     "gp_sobol_lds_points": (c_ll, [c_int]),
+    "gp_xval_max_fold": (c_int, []),
+    "gp_xval_ws_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "gp_xval": (c_int, [c_void_p, c_int, c_ll, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                        c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                        c_ll, c_void_p]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

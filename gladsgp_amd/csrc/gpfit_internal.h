@@ -10,6 +10,12 @@ hipError_t gpfit_trmv_launch(const double* Linv, int ld, long long sL, const dou
                              int ldw, double* z, int ldz, int rows, int n, int batch,
                              hipStream_t st);
 
+// gpfit_trmv_launch over all n rows that takes L[r,k] as zero for k > r whatever the buffer holds
+// there (gp_xval: the same bits as gpfit_trmv_launch on a buffer with a zeroed upper triangle).
+hipError_t gpfit_trmv_masked_launch(const double* Linv, int ld, long long sL, const double* w,
+                                    int ldw, double* z, int ldz, int n, int batch,
+                                    hipStream_t st);
+
 constexpr int GPFIT_POTRF_NB = 64;   // column block of gp_potrf_inv (chol.hip NB)
 
 // gp_potrf_inv_ws that also records `ev` on the stream once block step `k_ev` (NB = 64

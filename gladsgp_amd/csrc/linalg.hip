@@ -12,7 +12,11 @@ namespace {
 // z_b[r] = sum_{k<=r, k<n} Linv_b[r,k] w_b[k] for r0 <= r < rows.  1024 threads = 64 rows x 16
 // k-slices: each wave reads 64 consecutive rows of one column (512 B, coalesced), the 16
 // partial sums meet in LDS.  Reads the n^2/2 lower triangle once: HBM-bound.
+// kMask: take L[r,k] as zero for k > r whatever the buffer holds there (gp_xval, whose caller's
+// L^-1 need not have a zeroed upper triangle); without it the block's 64 x 64 diagonal square is
+// read as stored (zero in a gp_potrf_inv / gp_trtri buffer).  Equal bits on a zeroed buffer.
 constexpr int kTrmvSlices = 16;
+template <bool kMask>
 __global__ __launch_bounds__(1024) void trmv_kernel(const double* __restrict__ Linv, int ld,
                                                     long long sL, const double* __restrict__ w,
                                                     int ldw, double* __restrict__ z, int ldz,
@@ -25,13 +29,17 @@ __global__ __launch_bounds__(1024) void trmv_kernel(const double* __restrict__ L
   const double* wb = w + (long long)b * ldw;
   double acc0 = 0.0, acc1 = 0.0;
   const int kend = min(rb + 64, n);   // block-uniform bound; L is zero above r
+  auto at = [&](int k) {
+    const double v = L[r + (long long)k * ld];
+    return (kMask && k > r) ? 0.0 : v;
+  };
   if (r < rows) {
     int k = ks;
     for (; k + kTrmvSlices < kend; k += 2 * kTrmvSlices) {
-      acc0 = fma(L[r + (long long)k * ld], wb[k], acc0);
-      acc1 = fma(L[r + (long long)(k + kTrmvSlices) * ld], wb[k + kTrmvSlices], acc1);
+      acc0 = fma(at(k), wb[k], acc0);
+      acc1 = fma(at(k + kTrmvSlices), wb[k + kTrmvSlices], acc1);
     }
-    if (k < kend) acc0 = fma(L[r + (long long)k * ld], wb[k], acc0);
+    if (k < kend) acc0 = fma(at(k), wb[k], acc0);
   }
   __shared__ double red[kTrmvSlices][64];
   red[ks][threadIdx.x & 63] = acc0 + acc1;
@@ -83,8 +91,17 @@ hipError_t gpfit_trmv_rows_launch(const double* Linv, int ld, long long sL, cons
                                   int ldw, double* z, int ldz, int r0, int r1, int n, int batch,
                                   hipStream_t st) {
   if (r1 <= r0 || batch <= 0) return hipSuccess;
-  hipLaunchKernelGGL(trmv_kernel, dim3(gp_ceil_div(r1 - r0, 64), batch), dim3(1024), 0, st,
-                     Linv, ld, sL, w, ldw, z, ldz, r0, r1, n);
+  hipLaunchKernelGGL(trmv_kernel<false>, dim3(gp_ceil_div(r1 - r0, 64), batch), dim3(1024), 0,
+                     st, Linv, ld, sL, w, ldw, z, ldz, r0, r1, n);
+  return hipGetLastError();
+}
+
+hipError_t gpfit_trmv_masked_launch(const double* Linv, int ld, long long sL, const double* w,
+                                    int ldw, double* z, int ldz, int n, int batch,
+                                    hipStream_t st) {
+  if (n <= 0 || batch <= 0) return hipSuccess;
+  hipLaunchKernelGGL(trmv_kernel<true>, dim3(gp_ceil_div(n, 64), batch), dim3(1024), 0, st, Linv,
+                     ld, sL, w, ldw, z, ldz, 0, n, n);
   return hipGetLastError();
 }
 

@@ -399,15 +399,20 @@ class EmulatorPrediction:
             else:
                 mean_l = torch.empty((0, self.m), dtype=F64, device=dev)
                 var_l = torch.empty((0, self.m), dtype=F64, device=dev)
+        self._set_results(ctx, realize, seed,
+                          assemble_points(ctx, mean_l, var_l, self.m) if self.shard == "points"
+                          else assemble_units(ctx, mean_l, var_l, len(units)))
+
+    def _set_results(self, ctx, realize, seed, both) -> None:
+        """The tail every prediction shares: ``both`` = (mean, var) of the (sample, PC) units in
+        s-major order, each (S P, m) (None on the ranks that hold no result) -> the (S, m, P)
+        device arrays and the state ``.w`` / ``get_y()`` / ``summary()`` work from."""
+        S, P = self.S, self.P
         self.ctx = ctx
         self.realized = bool(realize)
         self.seed = int(np.random.SeedSequence().entropy & (2 ** 63 - 1)) if seed is None \
             else int(seed)
         self._w_dtype = np.dtype(np.float64)
-        if self.shard == "points":
-            both = assemble_points(ctx, mean_l, var_l, self.m)
-        else:
-            both = assemble_units(ctx, mean_l, var_l, len(units))
         if both is None:
             self.mean_dev = self.w_dev = self.var_dev = None
             return
@@ -664,8 +669,76 @@ def unit_order(rank_major: torch.Tensor, n_units: int, world: int) -> torch.Tens
     return rank_major[torch.as_tensor(inv, device=rank_major.device)]
 
 
-# SEPIA-compatible alias for drop-in call sites
+class EmulatorXvalPrediction(EmulatorPrediction):
+    """Cross-validated predictions of the n training simulations (SEPIA's
+    SepiaXvalEmulatorPrediction, assess_all_models.py:32, include_trunc_error.py:15): for every
+    fold F of ``leave_out_inds`` (a list of index lists; None = leave-one-out) and every
+    (sample, PC) GP, E[w_F | the other simulations] and its marginal variance, with the
+    hyperparameters, the PCA basis and w_hat of the full model (SEPIA refits neither per fold).
+
+    SEPIA refits one sub-model per fold; here each group of units is one gram -> potrf_inv ->
+    xval (gp_xval: every fold in closed form from L^-1).  The result is an
+    :class:`EmulatorPrediction` whose m = n points are the training simulations: row i of ``.w``
+    / ``.mean`` / ``.var`` is simulation i (rows in no fold are NaN), and ``get_y()`` /
+    ``summary()`` give the cross-validated field.  The variance is the one EmulatorPrediction
+    reports at a new point placed at t_i (``pred_nugget`` as there).  Folds hold at most
+    kernels.xval_max_fold() simulations.  Single device: ``ctx`` must be None."""
+
+    def __init__(self, leave_out_inds=None, model: EmulatorModel = None, samples: dict = None,
+                 pred_nugget: bool = True, budget_bytes: int = 2 << 30,
+                 group: int | None = None, ctx=None, realize: bool = False,
+                 seed: int | None = None):
+        if ctx is not None:
+            raise ValueError("ctx: cross-validation is not sharded over devices (pass None)")
+        if model is None or samples is None:
+            raise ValueError("EmulatorXvalPrediction needs model and samples")
+        self.model = model
+        dev = model.device
+        X = model.data.sim_data.t_dev
+        n = model.n
+        beta, s, delta, sp = gp_params(samples, _np(model.LamSim), model.d, model.P, pred_nugget)
+        S, P = s.shape
+        self.S, self.m, self.P = S, n, P
+        self.shard = "units"
+        self.lamWOs = np.asarray(samples["lamWOs"], dtype=np.float64).reshape(S)
+        self.leave_out_inds = None if leave_out_inds is None else \
+            [[int(i) for i in np.atleast_1d(f)] for f in leave_out_inds]
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)  # noqa
+        # units (s, j) in s-major order
+        beta_u, s_u, delta_u = t(beta.reshape(S * P, -1)), t(s.reshape(-1)), t(delta.reshape(-1))
+        shift_u = t((s + delta - sp).reshape(-1))
+        w_hat = model.w_hat.transpose(0, 1).contiguous()       # (P, n)
+        w_u = w_hat.repeat(S, 1)                               # (S P, n)
+        U = S * P
+        npad = kernels.padded_n(n)
+        g = max(1, int(budget_bytes // (8 * (n * n + npad * npad))))
+        if group is not None:
+            g = max(1, min(g, int(group)))
+        mean = torch.full((U, n), float("nan"), dtype=F64, device=dev)
+        var = torch.full((U, n), float("nan"), dtype=F64, device=dev)
+        for a in range(0, U, g):
+            b = min(U, a + g)
+            ch = kernels.cholesky_inverse(kernels.gram(X, beta_u[a:b], s_u[a:b], delta_u[a:b],
+                                                       batch=b - a))
+            ch.check()
+            kernels.xval(ch, w_u[a:b], self.leave_out_inds, shift_u[a:b],
+                         out=(mean[a:b], var[a:b]))
+        self.shift_dev = shift_u.reshape(S, 1, P)
+        self._set_results(None, realize, seed, (mean, var))
+
+    @property
+    def standardized_residuals(self) -> np.ndarray:
+        """(S, n, P): (w_hat - mean) / sqrt(var + shift), the PC-space residual of every
+        held-out simulation in units of the spread of the observed w_hat_i (shift = s + delta -
+        s_pred takes the predictive variance back to that of the observation)."""
+        w_hat = self.model.w_hat.unsqueeze(0)                  # (1, n, P)
+        r = (w_hat - self.mean_dev) / torch.sqrt(self.var_dev + self.shift_dev)
+        return r.cpu().numpy()
+
+
+# SEPIA-compatible aliases for drop-in call sites
 SepiaEmulatorPrediction = EmulatorPrediction
+SepiaXvalEmulatorPrediction = EmulatorXvalPrediction
 
 
 def default_data_dir():

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -367,6 +368,126 @@ def trmv(chol: Cholesky, w) -> torch.Tensor:
     _capi.call("gp_trmv", chol.linv_buf.data_ptr(), npad, npad * npad, n, w_t.data_ptr(), n,
                z.data_ptr(), n, batch, _stream(dev))
     return z
+
+
+def xval_max_fold() -> int:
+    return int(_capi.lib().gp_xval_max_fold())
+
+
+def _xval_folds(folds, n: int):
+    """Validate ``folds`` (a sequence of index sequences) on the host and return the CSR arrays
+    (fold_ptr, fold_idx) as int32 numpy, or (None, None) for leave-one-out over all n."""
+    if folds is None:
+        return None, None
+    fmax = xval_max_fold()
+    ptr, idx, seen = [0], [], set()
+    for k, fold in enumerate(folds):
+        fold = [fold] if np.isscalar(fold) else list(fold)
+        if len(fold) > fmax:
+            raise ValueError(f"folds: fold {k} holds {len(fold)} indices, more than "
+                             f"gp_xval_max_fold() = {fmax}")
+        for i in fold:
+            if int(i) != i:
+                raise ValueError(f"folds: index {i!r} of fold {k} is not an integer")
+            i = int(i)
+            if not 0 <= i < n:
+                raise ValueError(f"folds: index {i} of fold {k} is outside [0, {n})")
+            if i in seen:
+                raise ValueError(f"folds: index {i} appears twice (again in fold {k})")
+            seen.add(i)
+            idx.append(i)
+        ptr.append(len(idx))
+    return np.asarray(ptr, dtype=np.int32), np.asarray(idx, dtype=np.int32)
+
+
+class XvalNotPositiveDefinite(ValueError):
+    """A fold's Q_FF was not positive definite (info = fold + 1)."""
+
+
+def check_xval_info(info: torch.Tensor) -> None:
+    """:func:`check_info` for gp_xval's info: fold + 1 for a fold whose Q_FF is not positive
+    definite, -2 for a fold the library refused.  Synchronises with the device."""
+    vals = info.cpu()
+    bad = torch.nonzero(vals).flatten().tolist()
+    if not bad:
+        return
+    refused = [b for b in bad if int(vals[b]) < 0]
+    if refused:
+        raise ValueError(f"gp_xval refused a fold (info = -2: too large, or an index out of "
+                         f"range) for problems {refused}")
+    raise XvalNotPositiveDefinite(
+        f"Q_FF not positive definite (info = fold + 1 = {vals[bad].tolist()} for problems {bad})")
+
+
+_XVAL_WS = {}
+
+
+def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True):
+    """Cross-validated mean / variance of the training simulations from L^-1, no refit (gp_xval):
+    for every fold F, E[w_F | w outside F] and diag Cov - shift.  Returns (mean, var), each
+    (batch, n); entries whose index is in no fold are NaN (left as they are in ``out``).
+
+    ``folds``: a sequence of index sequences (each at most :func:`xval_max_fold` long, no index
+    twice), or None for leave-one-out; ``shift`` (batch,) or None for 0 (``s + delta - s_pred``
+    gives the variance :func:`predict` reports at a new point placed there); ``w`` a contiguous
+    float64 (batch, n) device tensor.  Everything is validated on the host before the call;
+    ``check`` synchronises and raises like :meth:`Cholesky.check`."""
+    if not isinstance(chol, Cholesky):
+        raise ValueError("chol: expected a kernels.Cholesky (padded L^-1)")
+    L = chol.linv_buf
+    dev, batch, n = L.device, L.shape[0], chol.n
+    npad = padded_n(n)
+    if not torch.is_tensor(w) or w.dtype != F64:
+        raise ValueError("w: expected a float64 tensor")
+    if w.dim() == 1:
+        w = w.reshape(1, -1)
+    if tuple(w.shape) != (batch, n):
+        raise ValueError(f"w: expected shape ({batch}, {n}), got {tuple(w.shape)}")
+    if not w.is_contiguous():
+        raise ValueError("w: expected a contiguous tensor")
+    ptr, idx = _xval_folds(folds, n)
+    if shift is not None:
+        if not torch.is_tensor(shift) or shift.dtype != F64 or shift.numel() != batch or \
+                not shift.is_contiguous():
+            raise ValueError(f"shift: expected a contiguous float64 tensor of {batch} values")
+    if out is not None:
+        if len(out) != 2 or any((not torch.is_tensor(t)) or t.dtype != F64 or
+                                tuple(t.shape) != (batch, n) or t.stride(1) != 1 or
+                                (batch > 1 and t.stride(0) < n) for t in out) or \
+                (batch > 1 and out[0].stride(0) != out[1].stride(0)):
+            raise ValueError(f"out: expected two float64 ({batch}, {n}) tensors with unit "
+                             "column stride and one row stride")
+    if L.dtype != F64 or tuple(L.shape) != (batch, npad, npad) or not L.is_contiguous():
+        raise ValueError(f"chol: expected a contiguous float64 ({batch}, {npad}, {npad}) L^-1")
+    for t, nm in ((L, "chol"), (w, "w")) + (((shift, "shift"),) if shift is not None else ()) + \
+            (tuple((t, "out") for t in out) if out is not None else ()):
+        _check_device(t, nm)
+    if out is None:
+        mean = torch.full((batch, n), float("nan"), dtype=F64, device=dev)
+        var = torch.full((batch, n), float("nan"), dtype=F64, device=dev)
+    else:
+        mean, var = out
+    ptr_t = idx_t = None
+    nfolds = nidx = 0
+    if ptr is not None:
+        nfolds, nidx = len(ptr) - 1, len(idx)
+        ptr_t = torch.as_tensor(ptr, device=dev)
+        # never an empty allocation: the library wants a pointer when folds are given
+        idx_t = torch.zeros(max(nidx, 1), dtype=torch.int32, device=dev)
+        if nidx:
+            idx_t[:nidx] = torch.as_tensor(idx, device=dev)
+    info = torch.empty(batch, dtype=torch.int32, device=dev)
+    nbytes = int(_capi.lib().gp_xval_ws_bytes(n, nfolds, nidx, batch))
+    ws = _XVAL_WS.setdefault(str(dev), Workspace()).get(nbytes, dev)
+    _capi.call("gp_xval", L.data_ptr(), npad, npad * npad, n, w.data_ptr(), n,
+               ptr_t.data_ptr() if ptr_t is not None else None,
+               idx_t.data_ptr() if idx_t is not None else None, nfolds, nidx,
+               shift.data_ptr() if shift is not None else None, mean.data_ptr(), var.data_ptr(),
+               mean.stride(0) if batch > 1 else n, info.data_ptr(), batch, ws.data_ptr(),
+               ws.numel(), _stream(dev))
+    if check:
+        check_xval_info(info)
+    return mean, var
 
 
 @dataclass

@@ -33,7 +33,7 @@
  *      - the L^-1 the prediction READS (gp_predict, gp_predict_ex, gp_predict_z,
  *        gp_predict_solve, gp_fit_predict's Linv) and both buffers of gp_pack_linv /
  *        gp_unpack_linv: 16-byte aligned base, even ldinv, even strideInv (gp_potrf_inv,
- *        gp_trtri, gp_trmv and gp_nll take any L^-1 layout);
+ *        gp_trtri, gp_trmv, gp_nll and gp_xval take any L^-1 layout);
  *      - every workspace `ws`: 256-byte aligned (gp_dgemm / gp_gemm_ex's split-K scratch and
  *        the `work` vectors of gp_nll / gp_mean_var: 8 bytes);
  *  - stream-ordered and asynchronous on `stream`; no host synchronisation, so calls can be
@@ -510,6 +510,43 @@ int gp_sobol_replicates(
     double* first, double* total, long long ldr, double* gfirst, double* gtotal, long long ldg,
     hipStream_t stream);
 long long gp_sobol_lds_points(int d);
+
+/* Cross-validated predictions of the training simulations (leave-one-out or K-fold) from the
+ * L^-1 of gp_potrf_inv, with no refit: what SEPIA's SepiaXvalEmulatorPrediction(leave_out_inds=)
+ * (imported by assess_all_models.py:32 and include_trunc_error.py:15) computes by refitting one
+ * sub-model per fold.  Per problem b, with A = G + delta I, Q = A^-1 = L^-T L^-1, z = L^-1 w and,
+ * for a fold F of f indices, the n x f column panel P_F = L^-1[:, F]:
+ *   Q_FF = P_F^T P_F,  alpha_F = P_F^T z,
+ *   mean[F] = w[F] - Q_FF^-1 alpha_F     = E[w_F | w outside F],
+ *   var[F]  = diag(Q_FF^-1) - shift[b]   (leave-one-out: w_i - alpha_i / Q_ii, 1 / Q_ii - shift).
+ * shift = s + delta - s_pred gives the variance gp_predict reports at a new point placed at x_i
+ * (s_pred on the diagonal); shift NULL or 0: the variance of the observed w_i.
+ *   Linv      the padded L^-1 of gp_potrf_inv (GPFIT_LINV_PADDED), ldinv >= gp_padded_n(n),
+ *             strideInv >= ldinv * gp_padded_n(n); any naturally aligned layout (a 16-B aligned
+ *             base with even ldinv and strideInv selects 16-B loads).  Column c is taken as
+ *             zero above row c and below row n - 1 whatever the buffer holds there.
+ *   w_hat     n values at w_hat + b * ldw.
+ *   fold_ptr  nfolds + 1 device ints, fold k = fold_idx[fold_ptr[k] .. fold_ptr[k + 1] - 1];
+ *   fold_idx  nidx <= n device ints, 0-based, in any order; both shared by all problems.  Both
+ *             NULL with nfolds = nidx = 0: leave-one-out over all n.  An index should appear in
+ *             one fold at most (otherwise which fold's value is kept is unspecified).
+ *   mean, var written at + b * ldo + i for every i in a fold; other elements are not touched.
+ *   info      (may be NULL) info[b] = 0, or k + 1 for the first fold k whose Q_FF is not positive
+ *             definite (that fold's outputs are NaN, the other folds are produced), or -2 when a
+ *             fold holds more than GPFIT_XVAL_MAX_FOLD indices, an index lies outside [0, n) or
+ *             fold_ptr is not a non-decreasing sequence within [0, nidx]: such a fold is skipped,
+ *             nothing is read or written for it.
+ *   ws        gp_xval_ws_bytes(n, nfolds, nidx, batch) bytes, 256-B aligned (z of every problem).
+ * Leave-one-out reads the lower triangle once (4 n^2 bytes per problem); a fold reads its panel
+ * from row min(F) down (8 (n - min F) f bytes).  Stream-ordered, allocates nothing, can be
+ * captured into a hipGraph.  n = 0 or batch = 0: no launch. */
+#define GPFIT_XVAL_MAX_FOLD 64
+int gp_xval_max_fold(void);
+long long gp_xval_ws_bytes(int n, int nfolds, int nidx, int batch);
+int gp_xval(const double* Linv, int ldinv, long long strideInv, int n, const double* w_hat,
+            int ldw, const int* fold_ptr, const int* fold_idx, int nfolds, int nidx,
+            const double* shift, double* mean, double* var, int ldo, int* info, int batch,
+            void* ws, long long ws_bytes, hipStream_t stream);
 
 /* out[0] = mean(x), out[1] = var(x, ddof) of a length-N vector (two-pass, deterministic);
  * work holds 1024 doubles.  np.var of the PC truncation residual, src/model.py:222. */
