@@ -46,9 +46,20 @@ template <int MODE>
 GP_DEV double* dk_ptr(double* Xb, int ldx, int k0) {
   return Xb + (MODE == kPotrf ? 0 : k0) + (long long)k0 * ldx;
 }
-#ifndef DIAG_PE
-#define DIAG_PE 4           // diag factor: steps between step-counter publications
-#endif
+
+// A batch of problems as the host side passes it to both factorisation paths: problem b's
+// matrix at A + b sA (leading dimension lda), its X -- L^-1, or the D_k scratch of kPotrf -- at
+// X + b sX (ldx); info / logdet per problem (either may be null).  The kernels keep scalar
+// arguments: taking this struct by value changed the code of every sweep kernel (their scalar
+// spills by 2 to 6) and of pp_kernel.
+struct Problem {
+  double* A; int lda; long long sA;
+  double* X; int ldx; long long sX;
+  int n, batch;
+  int* info; double* logdet;
+};
+
+constexpr int kDiagPublishEvery = 4;   // diag factor: steps between step-counter publications
 
 struct __align__(16) Smem {
   double As[NB * LP];
@@ -121,6 +132,24 @@ GP_DEV void store_op(double* S, const OpTile& t) {
   }
 }
 
+// acc (this wave's 32x32) += sum_k As[k][rows] * Bs[k][cols]: mma64 (below) without the zeroing.
+// Two bodies on purpose: with mma64 written as zeroing + mma64_add, pp_kernel's register
+// allocation moves (its scalar spills 270 -> 246, ~40 instructions), so the copy stays.
+GP_DEV void mma64_add(const double* As, const double* Bs, f64x4 (&acc)[2][2]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wr = w >> 1, wc = w & 1, li = lane & 15, lk = lane >> 4;
+#pragma unroll 4
+  for (int k4 = 0; k4 < NB / 4; ++k4) {
+    const int k = k4 + (NB / 4) * lk;
+    const double a0 = As[k * LP + wr * 32 + li], a1 = As[k * LP + wr * 32 + 16 + li];
+    const double b0 = Bs[k * LP + wc * 32 + li], b1 = Bs[k * LP + wc * 32 + 16 + li];
+    acc[0][0] = mfma16x16x4(a0, b0, acc[0][0]);
+    acc[0][1] = mfma16x16x4(a0, b1, acc[0][1]);
+    acc[1][0] = mfma16x16x4(a1, b0, acc[1][0]);
+    acc[1][1] = mfma16x16x4(a1, b1, acc[1][1]);
+  }
+}
+
 // acc (this wave's 32x32) = sum_k As[k][rows] * Bs[k][cols].  The MFMA's 4 k slots take rows
 // k4, k4+16, k4+32, k4+48 rather than 4 consecutive rows.  Measured: the factorisation inside
 // gp_fit_predict 3.47-3.49 -> 3.42-3.44 ms (same box, 3 reps, profiles/r01/ab_mma64_kslots.log);
@@ -168,7 +197,9 @@ GP_DEV void mma64_bt(const double* As, const double* Bt, f64x4 (&acc)[2][2]) {
   }
 }
 
-// Scatter the block's accumulator into LDS as Cs[col][row] (pitch LP).
+// Scatter the block's accumulator into LDS (pitch LP) as Cs[col][row], or row-major (RM) as
+// Cs[row][col].
+template <bool RM = false>
 GP_DEV void acc_to_lds(double* Cs, const f64x4 (&acc)[2][2]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wr = w >> 1, wc = w & 1, li = lane & 15, lk = lane >> 4;
@@ -179,7 +210,7 @@ GP_DEV void acc_to_lds(double* Cs, const f64x4 (&acc)[2][2]) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = wr * 32 + mi * 16 + lk + 4 * r, col = wc * 32 + nj * 16 + li;
-        Cs[col * LP + row] = acc[mi][nj][r];
+        Cs[RM ? row * LP + col : col * LP + row] = acc[mi][nj][r];
       }
 }
 
@@ -300,10 +331,10 @@ __device__ __attribute__((noinline)) int diag_factor_inv(int nb, double* ld_out)
         w[j + 1] = fma(-readlane_f64(wj, j + 1), t, w[j + 1]);
         M[j * NB + lane] = t;
         if constexpr (j + 2 < NB) bcast_axpy<j + 2>(w, &S[j * NB], t);
-        // publish every DIAG_PE steps (and the last): the release store is a scheduling
-        // barrier, and between publications the next column's pivot chain can overlap this
-        // column's trailing FMAs
-        if constexpr ((j + 1) % DIAG_PE == 0 || j + 2 == NB)
+        // publish every kDiagPublishEvery steps (and the last): the release store is a
+        // scheduling barrier, and between publications the next column's pivot chain can
+        // overlap this column's trailing FMAs
+        if constexpr ((j + 1) % kDiagPublishEvery == 0 || j + 2 == NB)
           __hip_atomic_store((int*)&sm.step, j + 1, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_WORKGROUP);
       }
@@ -328,14 +359,13 @@ __device__ __attribute__((noinline)) int diag_factor_inv(int nb, double* ld_out)
     double bq[NB];
 #pragma unroll
     for (int r = 0; r < NB; ++r) bq[r] = (r == lane) ? 1.0 : 0.0;
-#ifndef DIAG_PROBE_NO_INV   // tools/probe_diag.hip only: time wave 0's sweep alone
     static_for<0, NB - 1, 1>([&](auto J) {
       constexpr int j = decltype(J)::value;
-      if constexpr (j % DIAG_PE == 0)   // wave 0 publishes every DIAG_PE steps
-        lds_wait_ge((int*)&sm.step, (j + DIAG_PE < NB - 1) ? j + DIAG_PE : NB - 1);
+      if constexpr (j % kDiagPublishEvery == 0)   // wave 0's publication period
+        lds_wait_ge((int*)&sm.step,
+                    (j + kDiagPublishEvery < NB - 1) ? j + kDiagPublishEvery : NB - 1);
       bcast_axpy<j + 1>(bq, &M[j * NB], bq[j]);
     });
-#endif
     __syncthreads();   // invs from wave 0; every M read done
 #pragma unroll
     for (int r = 0; r < NB; ++r) sm.Bs[r * LP + lane] = bq[r] * sm.invs[r];
@@ -352,7 +382,7 @@ __device__ __attribute__((noinline)) int diag_factor_inv(int nb, double* ld_out)
 // ---- Blocked 64x64 factor + inverse (the persistent chain's diagonal step) -------------------
 // Same contract as diag_factor_inv (T = sm.As full symmetric [row][col] with identity padding
 // past nb; on return T = L, U = sm.Bs = L^-1, both lower with zero upper), on 16 x 16 blocks:
-//   for b = 0..3:  leaf16(b)                        wave 0: L_bb, Dinv_b = L_bb^-1
+//   for b = 0..3:  leaf16_blocked(b)                wave 0: L_bb, Dinv_b = L_bb^-1
 //                  L_rb = A_rb Dinv_b^T (r > b)     waves 1-3, one MFMA block each
 //                  A_rs -= L_rb L_sb^T (b < s <= r) wave 0 takes (b+1, b+1) and goes straight on
 //                                                   to the next leaf; waves 1-3 the rest
@@ -395,67 +425,23 @@ GP_DEV void st16(lds_double* Cb, const f64x4& a, double sg) {
 // The block lives in MFMA C layout (lane l, reg q = element [(l >> 4) + 4q][l & 15]), so row j
 // of the block is register j / 4 of lanes 16 (j % 4) .. + 15, which is at once the A operand's
 // column k = j % 4 (A[i][k] from lane 16k + i) and the B operand's row k (B[k][c] from lane
-// 16k + c).  Elimination step j is therefore ONE v_mfma_f64_16x16x4 on the whole block,
+// 16k + c).  Elimination step j can therefore be ONE v_mfma_f64_16x16x4 on the whole block,
 //   A[i][c] -= A[j][i] (A[j][c] / p_j)    (i, c > j; the other three k lanes zero),
 // and one more applies the same row operation to W (= I at the start): W[i][c] -= m_i W[j][c],
 // m_i = A[j][i] / p_j.  Both factors come from row j only, the same copy for every row (the
 // rounding asymmetry of the trailing block never feeds back; see diag_factor_inv).  At the end
 // A's lower triangle holds Lt[r][c] p_c and W = Lt^-1:  L = A D^-1/2 (columns), L^-1 = D^-1/2 W
-// (rows).  Per step the dependent chain is readlane -> rcp + 2 Newton -> select -> MFMA; the
-// register-resident form with one readlane pair per row and step (and the SGPR traffic that
-// came with it) measured 8.5k cycles per leaf (tools/dbg/leaf_micro.hip).  Splitting the W
-// row operations onto a second wave (multipliers handed over through LDS, a step counter)
-// measured slower inside the chain: 14.6 vs 12.4 us per 64 x 64 factor
+// (rows).  That per-column leaf (leaf16, now tools/dbg/leaf16.h: per step the dependent chain
+// readlane -> rcp + 2 Newton -> select -> MFMA) was the library's first; the register-resident
+// form before it, with one readlane pair per row and step (and the SGPR traffic that came with
+// it), measured 8.5k cycles per leaf (tools/dbg/leaf_micro.hip).  Splitting the W row
+// operations onto a second wave (multipliers handed over through LDS, a step counter) measured
+// slower inside the chain: 14.6 vs 12.4 us per 64 x 64 factor
 // (profiles/r03/pp_trace_pp4_pairs_splitleaf.txt).
-GP_DEV void leaf16(lds_double* T, lds_double* U, int o, lds_double* piv) {
-  const int lane = threadIdx.x & 63;
-  const int r0 = lane >> 4, c = lane & 15;
-  f64x4 A = ld16(T + o * LP + o);
-  f64x4 W;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) W[q] = (r0 + 4 * q == c) ? 1.0 : 0.0;
-  double colpiv = 1.0;          // p_c of this lane's column
-  double rowpiv[4];             // p_r of rows r0 + 4q
-#pragma unroll
-  for (int q = 0; q < 4; ++q) rowpiv[q] = 1.0;
-  static_for<0, 16, 1>([&](auto J) {
-    constexpr int j = decltype(J)::value;
-    constexpr int q = j >> 2, k = j & 3;
-    const double p = readlane_f64(A[q], 16 * k + j);
-    colpiv = (c == j) ? p : colpiv;
-    rowpiv[q] = (r0 == k) ? p : rowpiv[q];
-    if constexpr (j < 15) {
-      const double rp = rcp_nr(p);
-      const bool sel = r0 == k && c > j;
-      const double rowj = A[q];
-      const double a = sel ? -rowj : 0.0;
-      const double m = sel ? rowj * rp : 0.0;
-      const double wj = W[q];
-      A = mfma16x16x4(a, m, A);
-      W = mfma16x16x4(-m, wj, W);
-    }
-  });
-  const double rsc = rsqrt_nr(colpiv);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = r0 + 4 * q;
-    const double rsr = rsqrt_nr(rowpiv[q]);
-    T[(o + r) * LP + o + c] = r >= c ? A[q] * rsc : 0.0;
-    U[(o + r) * LP + o + c] = r >= c ? W[q] * rsr : 0.0;
-  }
-  if (lane < 16) piv[o + c] = colpiv;
-}
-
-#ifndef LEAF_MASKED
-#define LEAF_MASKED 1
-#endif
-#ifndef PP_LEAF_BLOCKED
-#define PP_LEAF_BLOCKED 1   // 0: leaf16 (one MFMA per column), 1: leaf16_blocked
-#endif
-
-// Blocked leaf (PP_LEAF_BLOCKED, the default): the same elimination four columns at a time.
-// At the start of block q (columns 4q .. 4q+3, whose rows are register q: lane 16k + c = row
-// 4q + k, column c) every row group receives all four of the block's rows (four lane shuffles
+//
+// leaf16_blocked runs that elimination four columns at a time.  At the start of block q
+// (columns 4q .. 4q+3, whose rows are register q: lane 16k + c = row 4q + k, column c) every
+// row group receives all four of the block's rows (four lane shuffles
 // for A, four for W), so lane 16k + c holds A[4q..4q+3][c]; the block's four elimination steps
 // are then lane-local FMAs whose multipliers A[j][4q+k] / p_j are wave-uniform (readlanes of
 // row j), and each lane takes its own row back.  ONE MFMA then applies the block's rank-4 update
@@ -494,32 +480,22 @@ GP_DEV void leaf16_blocked(lds_double* T, lds_double* U, int o, lds_double* piv)
       const double p = readlane_f64(t[jj], j);
       colpiv = (c == j) ? p : colpiv;
       rowpiv[q] = (r0 == jj) ? p : rowpiv[q];
-#if LEAF_MASKED
       // row j masked to the columns it still updates (c > j) while the pivot's reciprocal is
       // formed: the update below then needs no select on its dependency chain (columns c <= j
       // get fma(-m, 0, t) = t)
       const double tjm = (c > j) ? t[jj] : 0.0;
-#endif
       if constexpr (j < 15) {
         // 1 / p_j: v_rcp_f64's estimate (~2^-26: 1e-8 residuals alone) + one Newton step, as
         // accurate as two here (|LL^T - G| and |L^-1 L - I| unchanged on the micro-benchmark's
         // tiles) and one dependent FMA pair shorter: 22.7k vs 23.4k cycles per 64 x 64 factor
         // (profiles/r04/leaf_micro_nr*.log)
-#ifndef LEAF_NR
-#define LEAF_NR 1
-#endif
         double rp = __builtin_amdgcn_rcp(p);
-        if constexpr (LEAF_NR >= 1) rp = fma(rp, fma(-p, rp, 1.0), rp);
-        if constexpr (LEAF_NR >= 2) rp = fma(rp, fma(-p, rp, 1.0), rp);
+        rp = fma(rp, fma(-p, rp, 1.0), rp);
         rpk[jj] = rp;
         static_for<jj + 1, 4, 1>([&](auto K) {
           constexpr int k = decltype(K)::value;
           const double m = readlane_f64(t[jj], 4 * q + k) * rp;     // A[j][4q+k] / p_j
-#if LEAF_MASKED
           t[k] = fma(-m, tjm, t[k]);
-#else
-          t[k] = (c > j) ? fma(-m, t[jj], t[k]) : t[k];
-#endif
           tw[k] = fma(-m, tw[jj], tw[k]);
         });
       }
@@ -575,10 +551,7 @@ GP_DEV int diag_factor_blk(int nb, double* ld_out) {
     // while wave 0 factors leaf b, waves 1-2 build row b-1 of the inverse (its inputs -- Dinv of
     // rows <= b-1, the final L_{b-1,k}, the rows above -- are all complete), which the serial
     // phase after the last leaf used to do
-    if (w == 0) {
-      if constexpr (PP_LEAF_BLOCKED) leaf16_blocked(T, U, 16 * b, piv);
-      else leaf16(T, U, 16 * b, piv);
-    }
+    if (w == 0) leaf16_blocked(T, U, 16 * b, piv);
     else if (b >= 2 && w <= b - 1) inv_block(b - 1, w - 1);
     else if (b == 3 && w == 3) {
       // the last row's sums over the rows already final (k = c .. 1), beside leaf 3, into the
@@ -882,8 +855,8 @@ GP_DEV UpdTile upd_tile(double* Ab, int lda, double* Xb, int ldx, int n, int k, 
 
 // Global loads of one update tile into registers: the C tile (coalesced) and both operands.
 // Full tiles take a branch-free path: the code a cold instruction cache has to stream per
-// launch is what bounds these short kernels (tools/probe_update.hip: a worker's first tile
-// 22 us, its second 7 us).
+// launch is what bounds these short kernels (measured with a stand-alone probe of this kernel
+// that is no longer in the tree: a worker's first tile 22 us, its second 7 us).
 GP_DEV void upd_load(const UpdTile& t, int lda, int kv, OpTile& ta, OpTile& tb,
                      double (&cpre)[16]) {
   const int tid = threadIdx.x;
@@ -1094,6 +1067,32 @@ long long* g_trace_buf = nullptr;
 
 __shared__ int g_msg[4];              // dequeued task / wait results broadcast to the workgroup
 
+// The flag words of one problem, all 0 at the launch and set to 1 by the producer (abort: 1 a
+// non-PD pivot, 2 a spent poll budget).  The only place that knows the layout:
+// FL[N*N], FX[N*N], DPF[N], SPF[N], abort.
+struct PPFlags {
+  int* F; int N;
+  GP_HD static int words(int N) { return 2 * N * N + 2 * N + 1; }
+  GP_HD int* L(int i, int j) const { return F + i * N + j; }          // L_ij stored; (j, j): D_j
+  GP_HD int* X(int i, int c) const { return F + N * N + i * N + c; }  // X_ic stored (i > c)
+  // z_j stored (gp_loglik's in-chain mode, which has no X tiles): in the unused FX words
+  GP_HD int* Z(int j) const { return F + N * N + j; }
+  GP_HD int* DP(int j) const { return F + 2 * N * N + j; }            // DP(j)'s partial sums
+  GP_HD int* SP(int j) const { return F + 2 * N * N + N + j; }        // SP(j)'s partial sums
+  GP_HD int* abort() const { return F + 2 * N * N + 2 * N; }
+};
+
+// gp_loglik's in-chain mode (pp_kernel<true>, inv = 0): the right-hand sides w (problem b at
+// w + b ldw), the forward-substitution scratch zb (problem b at zb + b zld: z_j at j 64,
+// DP(j)'s partial sums zq_j at zq_off + j 64), per problem sum z^2 (zz), and the outputs
+// ll / status / info_out of gp_loglik.
+struct PPLoglik {
+  const double* w; int ldw;
+  double* zb; int zld, zq_off;
+  double* zz; double* ll; int* status; int* info_out;
+};
+
+// (the problem's fields spelled out rather than a Problem member: see Problem)
 struct PPArgs {
   double* A; long long sA; int lda;
   double* X; long long sX; int ldx;   // L^-1 (inv) or the 64 x 64N D_k scratch (plain)
@@ -1105,18 +1104,23 @@ struct PPArgs {
   int groups;                         // 1: one shared queue; 8: per-XCD queues (pp_groups)
   int* head;                          // [0] dequeue counter, [1] workgroups that have left,
                                       // [32 + 4g] group g's dequeue counter
-  int* flags; int fstride;            // per problem: FL[N*N], FX[N*N], DPF[N], SPF[N], abort
-  // gp_loglik's in-chain mode (pp_kernel<true>, inv = 0): the right-hand sides w (problem b at
-  // w + b ldw), the forward-substitution scratch zb (problem b at zb + b zld: z_j at j 64,
-  // DP(j)'s partial sums zq_j at zq_off + j 64), per problem sum z^2 (zz), and the outputs
-  // ll / status / info_out of gp_loglik.  FZ[j] (z_j stored) lives in the unused FX flags.
-  const double* w; int ldw;
-  double* zb; int zld, zq_off;
-  double* zz; double* ll; int* status; int* info_out;
+  int* flags; int fstride;            // problem b's PPFlags words at flags + b fstride
+  PPLoglik lik;                       // pp_kernel<true> only
+  GP_DEV PPFlags fl(int b) const { return PPFlags{flags + (long long)b * fstride, N}; }
 #ifdef GPFIT_PP_TRACE
   int* dbg;                           // trace build only: per-workgroup progress words
   long long* trace;                   // trace build only: per-task / per-chain-step stamps
 #endif
+};
+
+// Problem b's 64 x 64 tiles: A's tile (r, c), X's tile (r, c), the valid rows of tile row r.
+struct PPTiles {
+  const PPArgs& P;
+  double *Ab, *Xb;
+  GP_DEV PPTiles(const PPArgs& P_, int b) : P(P_), Ab(P_.A + b * P_.sA), Xb(P_.X + b * P_.sX) {}
+  GP_DEV double* a(int r, int c) const { return Ab + r * NB + (long long)c * NB * P.lda; }
+  GP_DEV double* x(int r, int c) const { return Xb + r * NB + (long long)c * NB * P.ldx; }
+  GP_DEV int rv(int r) const { return min(NB, P.n - r * NB); }
 };
 
 GP_DEV long long pp_now() { return (long long)__builtin_amdgcn_s_memrealtime(); }
@@ -1281,37 +1285,6 @@ GP_DEV void pp_publish(int* flag) {
   if (threadIdx.x == 0) pp_stflag(flag, 1);
 }
 
-// acc (this wave's 32x32) += sum_k As[k][rows] * Bs[k][cols]   (mma64 without the zeroing)
-GP_DEV void mma64_add(const double* As, const double* Bs, f64x4 (&acc)[2][2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wr = w >> 1, wc = w & 1, li = lane & 15, lk = lane >> 4;
-#pragma unroll 4
-  for (int k4 = 0; k4 < NB / 4; ++k4) {
-    const int k = k4 + (NB / 4) * lk;
-    const double a0 = As[k * LP + wr * 32 + li], a1 = As[k * LP + wr * 32 + 16 + li];
-    const double b0 = Bs[k * LP + wc * 32 + li], b1 = Bs[k * LP + wc * 32 + 16 + li];
-    acc[0][0] = mfma16x16x4(a0, b0, acc[0][0]);
-    acc[0][1] = mfma16x16x4(a0, b1, acc[0][1]);
-    acc[1][0] = mfma16x16x4(a1, b0, acc[1][0]);
-    acc[1][1] = mfma16x16x4(a1, b1, acc[1][1]);
-  }
-}
-
-// The block's accumulator into LDS row-major: Cs[row][col] (pitch LP).
-GP_DEV void acc_to_lds_rm(double* Cs, const f64x4 (&acc)[2][2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wr = w >> 1, wc = w & 1, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wr * 32 + mi * 16 + lk + 4 * r, col = wc * 32 + nj * 16 + li;
-        Cs[row * LP + col] = acc[mi][nj][r];
-      }
-}
-
 // Wait until the flag *f is set, or the problem aborted / the poll budget ran out (then
 // false).  One lane polls; the verdict is broadcast through g_msg (all threads call).
 GP_DEV bool pp_wait1(const int* f, int* abort, long long budget) {
@@ -1359,12 +1332,8 @@ struct PPTask {
 
 template <bool LL>
 GP_DEV PPTerm pp_term(const PPArgs& P, const PPTask& T, int t) {
-  const int N = P.N;
-  double* Ab = P.A + T.b * P.sA;
-  double* Xb = P.X + T.b * P.sX;
-  const int* F = P.flags + (long long)T.b * P.fstride;
-  auto atile = [&](int r, int c) { return Ab + r * NB + (long long)c * NB * P.lda; };
-  auto rv = [&](int r) { return min(NB, P.n - r * NB); };
+  const PPFlags F = P.fl(T.b);
+  const PPTiles S(P, T.b);
   PPTerm u;
   u.lda_ = P.lda;
   u.ldb_ = P.lda;
@@ -1381,26 +1350,26 @@ GP_DEV PPTerm pp_term(const PPArgs& P, const PPTask& T, int t) {
   // cache line spans two tiles (section comment), else sc1 as well.
   auto hz = [&](int r, int k) { return r - k <= 1 || !P.plain; };
   if (T.kind == kTL || T.kind == kTSP) {   // L_ik L_jk^T with (i, j) = (T.i, T.j)
-    u.a = atile(T.i, t);  u.fa = F + T.i * N + t;  u.av = rv(T.i);  u.ca = hz(T.i, t);
-    u.b = atile(T.j, t);  u.fb = F + T.j * N + t;  u.bv = rv(T.j);  u.cb = hz(T.j, t);
+    u.a = S.a(T.i, t);  u.fa = F.L(T.i, t);  u.av = S.rv(T.i);  u.ca = hz(T.i, t);
+    u.b = S.a(T.j, t);  u.fb = F.L(T.j, t);  u.bv = S.rv(T.j);  u.cb = hz(T.j, t);
   } else if (T.kind == kTDP) {             // L_jk L_jk^T
-    u.a = atile(T.j, t);  u.fa = F + T.j * N + t;  u.av = rv(T.j);  u.ca = hz(T.j, t);
-    u.b = u.a;            u.fb = u.fa;             u.bv = u.av;     u.cb = u.ca;
-    if constexpr (LL) u.fc = F + N * N + t;  // (+ L_jk z_k: z_k stored by chain step k, FZ[k])
+    u.a = S.a(T.j, t);  u.fa = F.L(T.j, t);  u.av = S.rv(T.j);  u.ca = hz(T.j, t);
+    u.b = u.a;          u.fb = u.fa;         u.bv = u.av;       u.cb = u.ca;
+    if constexpr (LL) u.fc = F.Z(t);       // (+ L_jk z_k: z_k stored by chain step k)
   } else {                                 // XT: L_ik X_kc, k = c + t (X_cc = D_c)
     const int k = T.j + t;
-    u.a = atile(T.i, k);  u.fa = F + T.i * N + k;  u.av = rv(T.i);  u.ca = hz(T.i, k);
+    u.a = S.a(T.i, k);  u.fa = F.L(T.i, k);  u.av = S.rv(T.i);  u.ca = hz(T.i, k);
     u.cb = !P.plain;
-    u.b = Xb + k * NB + (long long)T.j * NB * P.ldx;
+    u.b = S.x(k, T.j);
     u.ldb_ = P.ldx;
-    u.fb = (k == T.j) ? F + k * N + k : F + N * N + k * N + T.j;
+    u.fb = (k == T.j) ? F.L(k, k) : F.X(k, T.j);
     u.bv = NB;                               // X is zero-padded to npad: always in bounds
     u.btrn = true;
     if (T.kind == kTX2 && k > T.j) {         // + L_ik X_k,c+1 (X_c+1,c+1 = D_c+1)
       const int c1 = T.j + 1;
-      u.c = Xb + k * NB + (long long)c1 * NB * P.ldx;
+      u.c = S.x(k, c1);
       u.ldc_ = P.ldx;
-      u.fc = (k == c1) ? F + k * N + k : F + N * N + k * N + c1;
+      u.fc = (k == c1) ? F.L(k, k) : F.X(k, c1);
       u.cc = !P.plain;
     }
   }
@@ -1470,7 +1439,7 @@ GP_DEV bool pp_accumulate(const PPArgs& P, const PPTask& T, f64x4 (&acc)[2][2],
   double zr = 0.0;                                   // z_k of the term in flight (tid < 64)
   auto ldz = [&](int t) {
     if (lldp && threadIdx.x < 64)
-      zr = __hip_atomic_load(P.zb + (long long)T.b * P.zld + t * NB + threadIdx.x,
+      zr = __hip_atomic_load(P.lik.zb + (long long)T.b * P.lik.zld + t * NB + threadIdx.x,
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   OpTile ta, tb, tc;
@@ -1553,29 +1522,18 @@ GP_DEV double* pp_dptr(const PPArgs& P, int b, int j, int& ld) {
 
 // The persistent kernel's two task families are inlined into its dispatch loop, where their
 // register allocations add up (chain alone 344 VGPRs+AGPRs, workers alone 350, both 462: room
-// for one 48-register cross-covariance wave per SIMD beside it).  As calls (PP_TASK_CALLS=1)
-// the kernel takes 353 (+176 B of scratch per lane for the call frames), room for three; the
-// cross-covariance then ran 1.09 instead of ~2 ms per C3 step, but the factorisation took 2.17
-// instead of 1.81 ms alone and 2.40 beside it, and the C3 step got slower (27.05-27.21 ms,
-// profiles/r04/r04d_*; same-box A/B in r04e_*).
-#ifndef PP_TASK_CALLS
-#define PP_TASK_CALLS 0
-#endif
-#if PP_TASK_CALLS
-#define PP_TASK __device__ __attribute__((noinline))
-#else
-#define PP_TASK GP_DEV
-#endif
-
+// for one 48-register cross-covariance wave per SIMD beside it).  As calls (pp_chain and
+// pp_worker noinline) the kernel takes 353 (+176 B of scratch per lane for the call frames),
+// room for three; the cross-covariance then ran 1.09 instead of ~2 ms per C3 step, but the
+// factorisation took 2.17 instead of 1.81 ms alone and 2.40 beside it, and the C3 step got
+// slower (27.05-27.21 ms, profiles/r04/r04d_*; same-box A/B in r04e_*).
 template <bool LL>
-PP_TASK void pp_worker(const PPArgs& P, const PPTask& T) {
+GP_DEV void pp_worker(const PPArgs& P, const PPTask& T) {
   Smem& sm = g_sm;
-  const int N = P.N;
-  int* F = P.flags + (long long)T.b * P.fstride;
-  int* abort = F + 2 * N * N + 2 * N;
+  const PPFlags F = P.fl(T.b);
+  int* abort = F.abort();
   if (pp_ldflag(abort)) return;
-  double* Ab = P.A + T.b * P.sA;
-  double* Xb = P.X + T.b * P.sX;
+  const PPTiles S(P, T.b);
   f64x4 acc[2][2], acc2[2][2];
   PP_MARK(P, 20 + T.kind, T.i * 1000 + T.j);
   PP_STALL_RESET();
@@ -1584,15 +1542,12 @@ PP_TASK void pp_worker(const PPArgs& P, const PPTask& T) {
   PP_TRACE(P, tr + 1, pp_now());
   PP_TRACE(P, tr + 4, T.kind | (T.b << 4));
   PP_TRACE(P, tr + 5, T.i | (T.j << 16));
-  auto atile = [&](int r, int c) { return Ab + r * NB + (long long)c * NB * P.lda; };
-  auto xtile = [&](int r, int c) { return Xb + r * NB + (long long)c * NB * P.ldx; };
-  auto rv = [&](int r) { return min(NB, P.n - r * NB); };
   const bool xt = T.kind == kTX || T.kind == kTX2;
   // the task's own A tile (DP / SP: the chain's partial-sum tile; LT: A_ij), in flight from
   // here until the epilogue
   const int ar = T.kind == kTDP ? T.j : (T.kind == kTSP ? T.j + 1 : T.i);
   OpTile ta;
-  if (!xt) pp_load(ta, atile(ar, T.j), P.lda, rv(ar), T.kind == kTL ? NB : rv(T.j));
+  if (!xt) pp_load(ta, S.a(ar, T.j), P.lda, S.rv(ar), T.kind == kTL ? NB : S.rv(T.j));
   double zq;
   if (!pp_accumulate<LL>(P, T, acc, acc2, abort, zq)) return;
   PP_MARK(P, 30 + T.kind, T.i * 1000 + T.j);
@@ -1602,32 +1557,32 @@ PP_TASK void pp_worker(const PPArgs& P, const PPTask& T) {
   if (T.kind == kTDP || T.kind == kTSP) {
     // partial sums for the chain, in place in A
     const int r = ar;
-    double* dst = atile(r, T.j);
-    pp_sub_tile(ta, rv(r), rv(T.j), T.kind == kTDP, acc);
-    pp_store_cm(dst, P.lda, sm.As, rv(r), rv(T.j), false, T.kind == kTDP);
+    double* dst = S.a(r, T.j);
+    pp_sub_tile(ta, S.rv(r), S.rv(T.j), T.kind == kTDP, acc);
+    pp_store_cm(dst, P.lda, sm.As, S.rv(r), S.rv(T.j), false, T.kind == kTDP);
     if constexpr (LL) {
       if (T.kind == kTDP) {
         // zq_j = sum_{k < j-1} L_jk z_k for the chain's y_j: the four column quarters' partial
         // sums added in quarter order (a fixed order)
         g_ll[kLLPart + threadIdx.x] = zq;
         __syncthreads();
-        if (threadIdx.x < 64 && threadIdx.x < rv(T.j)) {
+        if (threadIdx.x < 64 && threadIdx.x < S.rv(T.j)) {
           const double* pq = g_ll + kLLPart + threadIdx.x;
-          __hip_atomic_store(P.zb + (long long)T.b * P.zld + P.zq_off + T.j * NB + threadIdx.x,
-                             ((pq[0] + pq[64]) + pq[128]) + pq[192], __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(
+              P.lik.zb + (long long)T.b * P.lik.zld + P.lik.zq_off + T.j * NB + threadIdx.x,
+              ((pq[0] + pq[64]) + pq[128]) + pq[192], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
     }
-    pp_publish(T.kind == kTDP ? F + 2 * N * N + T.j : F + 2 * N * N + N + T.j);
+    pp_publish(T.kind == kTDP ? F.DP(T.j) : F.SP(T.j));
     PP_TRACE(P, tr + 3, pp_now());
     return;
   }
   if (T.kind == kTL) {
     // L_ij = (A_ij - acc) D_j^T
-    double* dst = atile(T.i, T.j);
-    pp_sub_tile(ta, rv(T.i), NB, false, acc);
-    if (!pp_wait1(F + T.j * N + T.j, abort, P.budget)) return;
+    double* dst = S.a(T.i, T.j);
+    pp_sub_tile(ta, S.rv(T.i), NB, false, acc);
+    if (!pp_wait1(F.L(T.j, T.j), abort, P.budget)) return;
     int ldd;
     const double* D = pp_dptr(P, T.b, T.j, ldd);
     OpTile td;
@@ -1638,15 +1593,15 @@ PP_TASK void pp_worker(const PPArgs& P, const PPTask& T) {
     __syncthreads();
     acc_to_lds(sm.As, acc);
     __syncthreads();
-    pp_store_cm(dst, P.lda, sm.As, rv(T.i), NB, false);
-    pp_publish(F + T.i * N + T.j);
+    pp_store_cm(dst, P.lda, sm.As, S.rv(T.i), NB, false);
+    pp_publish(F.L(T.i, T.j));
     PP_TRACE(P, tr + 3, pp_now());
     return;
   }
   // XT: X_ic = -D_i S, S = acc (XT2: X_i,c+1 = -D_i S2, S2 = acc2), through g_keep
   __syncthreads();
-  acc_to_lds_rm(sm.Bs, acc);                            // Bs[p][cc] = S[p][cc]
-  if (!pp_wait1(F + T.i * N + T.i, abort, P.budget)) return;
+  acc_to_lds<true>(sm.Bs, acc);                         // Bs[p][cc] = S[p][cc]
+  if (!pp_wait1(F.L(T.i, T.i), abort, P.budget)) return;
   PP_MARK(P, 40, T.i * 1000 + T.j);
   int ldd;
   const double* D = pp_dptr(P, T.b, T.i, ldd);
@@ -1658,21 +1613,21 @@ PP_TASK void pp_worker(const PPArgs& P, const PPTask& T) {
   __syncthreads();
   acc_to_lds(g_keep, acc);
   __syncthreads();
-  pp_store_cm(xtile(T.i, T.j), P.ldx, g_keep, NB, NB, true);
+  pp_store_cm(S.x(T.i, T.j), P.ldx, g_keep, NB, NB, true);
   if (T.kind == kTX2) {
-    acc_to_lds_rm(sm.Bs, acc2);                         // (the barrier above: Bs read)
+    acc_to_lds<true>(sm.Bs, acc2);                        // (the barrier above: Bs read)
     __syncthreads();                                    // ... and every wave's g_keep reads
     mma64(sm.As, sm.Bs, acc2);
     __syncthreads();
     acc_to_lds(g_keep, acc2);
     __syncthreads();
-    pp_store_cm(xtile(T.i, T.j + 1), P.ldx, g_keep, NB, NB, true);
+    pp_store_cm(S.x(T.i, T.j + 1), P.ldx, g_keep, NB, NB, true);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-    pp_stflag(F + N * N + T.i * N + T.j, 1);
-    if (T.kind == kTX2) pp_stflag(F + N * N + T.i * N + T.j + 1, 1);
+    pp_stflag(F.X(T.i, T.j), 1);
+    if (T.kind == kTX2) pp_stflag(F.X(T.i, T.j + 1), 1);
   }
   PP_MARK(P, 41, T.i * 1000 + T.j);
   PP_TRACE(P, tr + 3, pp_now());
@@ -1695,7 +1650,7 @@ GP_DEV void ll_zstep(const PPArgs& P, int b, int j, int nb, double& zz) {
     const double z = r < nb ? ((pq[0] + pq[64]) + pq[128]) + pq[192] : 0.0;
     g_ll[kLLZ + r] = z;
     if (r < nb)
-      __hip_atomic_store(P.zb + (long long)b * P.zld + j * NB + r, z, __ATOMIC_RELAXED,
+      __hip_atomic_store(P.lik.zb + (long long)b * P.lik.zld + j * NB + r, z, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
     double q = z * z;
 #pragma unroll
@@ -1706,13 +1661,12 @@ GP_DEV void ll_zstep(const PPArgs& P, int b, int j, int nb, double& zz) {
 }
 
 template <bool LL>
-PP_TASK void pp_chain(const PPArgs& P, int b) {
+GP_DEV void pp_chain(const PPArgs& P, int b) {
   Smem& sm = g_sm;
   const int N = P.N;
-  int* F = P.flags + (long long)b * P.fstride;
-  int* abort = F + 2 * N * N + 2 * N;
-  double* Ab = P.A + b * P.sA;
-  auto atile = [&](int r, int c) { return Ab + r * NB + (long long)c * NB * P.lda; };
+  const PPFlags F = P.fl(b);
+  const PPTiles S(P, b);
+  int* abort = F.abort();
   double ld_sum = 0.0;
   double zz = 0.0;           // (LL) sum of z^2 so far (thread 0)
   OpTile tpj;                // P_jj, loaded by the previous step when its partials were ready
@@ -1737,17 +1691,18 @@ PP_TASK void pp_chain(const PPArgs& P, int b) {
     // staged in Bs ([col][row]), then every thread writes its own 16 accumulator positions
     // (mirrored to the lower element of P), identity padding past nb.
     if (!pref) {
-      if (j >= 2 && !pp_wait1(F + 2 * N * N + j, abort, P.budget)) return;
-      pp_load(tpj, atile(j, j), P.lda, nb, nb);
+      if (j >= 2 && !pp_wait1(F.DP(j), abort, P.budget)) return;
+      pp_load(tpj, S.a(j, j), P.lda, nb, nb);
     }
     // (LL) this step's right-hand side w_j and DP(j)'s partial sum zq_j (its flag is set here)
     double wq = 0.0;
     if constexpr (LL) {
       if (threadIdx.x < 64 && threadIdx.x < nb) {
-        wq = P.w[(long long)b * P.ldw + j * NB + threadIdx.x];
+        wq = P.lik.w[(long long)b * P.lik.ldw + j * NB + threadIdx.x];
         if (j >= 2)
-          wq -= __hip_atomic_load(P.zb + (long long)b * P.zld + P.zq_off + j * NB + threadIdx.x,
-                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          wq -= __hip_atomic_load(
+              P.lik.zb + (long long)b * P.lik.zld + P.lik.zq_off + j * NB + threadIdx.x,
+              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     PP_TRACE(P, tb0 + 1, pp_now());
@@ -1798,9 +1753,9 @@ PP_TASK void pp_chain(const PPArgs& P, int b) {
     if (j + 1 >= N) {
       // last step: D_j -> X_jj (or the D scratch), L_jj -> A (lower, LAPACK layout)
       pp_store_rm(D, ldd, sm.Bs, nb, false, true);
-      pp_store_rm(atile(j, j), P.lda, sm.As, nb, true);
+      pp_store_rm(S.a(j, j), P.lda, sm.As, nb, true);
       if constexpr (LL) ll_zstep(P, b, j, nb, zz);
-      pp_publish(F + j * N + j);
+      pp_publish(F.L(j, j));
       PP_TRACE(P, tb0 + 4, pp_now());
       break;
     }
@@ -1813,22 +1768,22 @@ PP_TASK void pp_chain(const PPArgs& P, int b) {
     // (zero padding past nb: X's rows >= n come out 0 in the XT tasks)
     pp_store_rm(D, ldd, sm.Bs, nb, false, true);
     OpTile tp;
-    const bool spref = j < 1 || pp_test1(F + 2 * N * N + N + j);
-    if (spref) pp_load(tp, atile(j + 1, j), P.lda, nb1, NB);
-    pref = j + 1 < 2 || pp_test1(F + 2 * N * N + j + 1);
-    if (pref) pp_load(tpj, atile(j + 1, j + 1), P.lda, nb1, nb1);
-    pp_publish(F + j * N + j);                          // drains stores and loads alike
+    const bool spref = j < 1 || pp_test1(F.SP(j));
+    if (spref) pp_load(tp, S.a(j + 1, j), P.lda, nb1, NB);
+    pref = j + 1 < 2 || pp_test1(F.DP(j + 1));
+    if (pref) pp_load(tpj, S.a(j + 1, j + 1), P.lda, nb1, nb1);
+    pp_publish(F.L(j, j));                          // drains stores and loads alike
     // L_jj (read by nobody in this launch) after D_j's flag: its stores drain under the GEMM
     // instead of in front of the flag (n = 4096 1.812 vs 1.824 ms, n = 1024 x 32 0.994 vs
     // 0.998, bit-identical; profiles/r04/ab_zt_ljj.log)
-    pp_store_rm(atile(j, j), P.lda, sm.As, nb, true);
+    pp_store_rm(S.a(j, j), P.lda, sm.As, nb, true);
     // (LL) z_j = D_j y_j (D_j in Bs) here, where the chain may wait for SP(j) below anyway
     if constexpr (LL) ll_zstep(P, b, j, nb, zz);
     __syncthreads();                                    // every wave has read As
     PP_TRACE(P, tb0 + 4, pp_now());
     if (!spref) {
-      if (!pp_wait1(F + 2 * N * N + N + j, abort, P.budget)) return;
-      pp_load(tp, atile(j + 1, j), P.lda, nb1, NB);    // As[p][r] = P[r][p]
+      if (!pp_wait1(F.SP(j), abort, P.budget)) return;
+      pp_load(tp, S.a(j + 1, j), P.lda, nb1, NB);    // As[p][r] = P[r][p]
     }
     store_op<false>(sm.As, tp);                         // (pp_publish's barrier: As is free)
     __syncthreads();
@@ -1841,7 +1796,7 @@ PP_TASK void pp_chain(const PPArgs& P, int b) {
     acc_to_lds(g_keep, acc);                           // keep[c][r] = L_j+1,j(r, c)
     __syncthreads();
     PP_TRACE(P, tb0 + 6, pp_now());
-    pp_store_cm(atile(j + 1, j), P.lda, g_keep, nb1, NB, false);
+    pp_store_cm(S.a(j + 1, j), P.lda, g_keep, nb1, NB, false);
     // the next step's SYRK runs while L_j+1,j's stores drain, then its flag goes up
     mma64(g_keep, g_keep, syrk);
     if constexpr (LL) {
@@ -1853,15 +1808,15 @@ PP_TASK void pp_chain(const PPArgs& P, int b) {
       for (int c = 0; c < 16; ++c) part = fma(g_keep[(c0 + c) * LP + r], g_ll[kLLZ + c0 + c], part);
       g_ll[kLLPart + threadIdx.x] = part;
     }
-    pp_publish(F + (j + 1) * N + j);
+    pp_publish(F.L(j + 1, j));
     if constexpr (LL)
-      if (threadIdx.x == 0) pp_stflag(F + N * N + j, 1);    // FZ[j]: z_j drained with the above
+      if (threadIdx.x == 0) pp_stflag(F.Z(j), 1);       // z_j drained with the above
     PP_MARK(P, 15, j);
     PP_TRACE(P, tb0 + 7, pp_now());
   }
   if (threadIdx.x == 0 && P.logdet) P.logdet[b] = ld_sum;
   if constexpr (LL)
-    if (threadIdx.x == 0) P.zz[b] = zz;
+    if (threadIdx.x == 0) P.lik.zz[b] = zz;
 }
 
 // The last workgroup to leave the launch (every task, chain and XT alike, has returned by then)
@@ -1878,15 +1833,14 @@ GP_DEV void pp_exit(const PPArgs& P) {
                                           __HIP_MEMORY_SCOPE_AGENT);
   if (done != (int)gridDim.x - 1 || !P.info) return;
   for (int b = 0; b < P.batch; ++b) {
-    const int* ab = P.flags + (long long)b * P.fstride + 2 * P.N * P.N + 2 * P.N;
-    if (pp_ldflag(ab) == 2) P.info[b] = -1;
+    if (pp_ldflag(P.fl(b).abort()) == 2) P.info[b] = -1;
     if constexpr (LL) {
       const int f = P.info[b];
-      const double v = 0.5 * P.zz[b] + 0.5 * P.logdet[b];
-      P.ll[b] = f < 0 ? __builtin_nan("") : -(f > 0 ? __builtin_huge_val() : v);
-      if (P.info_out) P.info_out[b] = f;
-      if (f < 0 && P.status)
-        __hip_atomic_fetch_or(P.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const double v = 0.5 * P.lik.zz[b] + 0.5 * P.logdet[b];
+      P.lik.ll[b] = f < 0 ? __builtin_nan("") : -(f > 0 ? __builtin_huge_val() : v);
+      if (P.lik.info_out) P.lik.info_out[b] = f;
+      if (f < 0 && P.lik.status)
+        __hip_atomic_fetch_or(P.lik.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -2069,7 +2023,7 @@ __global__ __launch_bounds__(1024) void pp_schedule_kernel(int2* tasks, int N, i
   // (after the barriers above: this block's zeroing is complete)
   if (T == 0)
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
-      if (preset_abort) flags[(long long)b * fstride + 2 * N * N + 2 * N] = 2;
+      if (preset_abort) *PPFlags{flags + (long long)b * fstride, N}.abort() = 2;
       tasks[b] = make_int2(kTChain | (b << 4), 0);
     }
   if (T >= nk) return;
@@ -2101,45 +2055,34 @@ static_assert(GPFIT_POTRF_NB == NB, "gpfit_internal.h must match the blocking");
 // Grid of chol_update_kernel for nt tiles per problem, capped at two resident blocks per CU
 // over the whole batch so every worker is resident and walks several tiles.
 static int update_grid(int nt, int batch) {
-  static const int cap_all = [] {
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        ncu <= 0)
-      ncu = 256;
-    return 2 * ncu;
-  }();
-  int cap = cap_all / (batch > 0 ? batch : 1);
+  int cap = 2 * gp_num_cus() / (batch > 0 ? batch : 1);
   if (cap < 2) cap = 2;
   return nt < cap ? nt : cap;
 }
 
-#define GP_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return GPFIT_ERR_HIP - (int)e_; } while (0)
-
-// The blocked sweep shared by the three entry points (arguments already validated; X is L^-1
+// The blocked sweep shared by the three entry points (arguments already validated; p.X is L^-1
 // (kPotrfInv, kTrtri, zero-filled by the caller) or the D_k scratch (kPotrf)).
 template <int MODE>
-static int potrf_sweep(double* A, int n, int lda, long long sA, double* X, int ldx, long long sX,
-                       int batch, int* info, double* logdet, hipStream_t stream, int k_ev,
-                       hipEvent_t ev) {
-  const int N = gp_ceil_div(n, NB);
+static int potrf_sweep(const Problem& p, hipStream_t stream, int k_ev, hipEvent_t ev) {
+  const int N = gp_ceil_div(p.n, NB), batch = p.batch;
   if (MODE != kTrtri) {   // kTrtri: every D_k is made up front by trtri_diag_kernel
-    hipLaunchKernelGGL(chol_diag_kernel<MODE>, dim3(batch), dim3(256), 0, stream, A, lda, sA, X,
-                       ldx, sX, n, 0, info, logdet);
+    hipLaunchKernelGGL(chol_diag_kernel<MODE>, dim3(batch), dim3(256), 0, stream, p.A, p.lda,
+                       p.sA, p.X, p.ldx, p.sX, p.n, 0, p.info, p.logdet);
     GP_CK(hipGetLastError());
   }
   for (int k = 0; k < N; ++k) {
     const int T = N - k - 1;
     const int npanel = MODE == kPotrfInv ? T + k : (MODE == kPotrf ? T : k);
     if (npanel > 0) {
-      hipLaunchKernelGGL(chol_panel_kernel<MODE>, dim3(npanel, batch), dim3(256), 0, stream, A,
-                         lda, sA, X, ldx, sX, n, k, T, info);
+      hipLaunchKernelGGL(chol_panel_kernel<MODE>, dim3(npanel, batch), dim3(256), 0, stream,
+                         p.A, p.lda, p.sA, p.X, p.ldx, p.sX, p.n, k, T, p.info);
       GP_CK(hipGetLastError());
     }
     if (T > 0) {
       const int nt = (MODE == kTrtri ? 0 : T * (T + 1) / 2) + (MODE == kPotrf ? 0 : T * (k + 1));
-      hipLaunchKernelGGL(chol_update_kernel<MODE>, dim3(update_grid(nt, batch), batch), dim3(256), 0, stream, A,
-                         lda, sA, X, ldx, sX, n, k, T, info, logdet);
+      hipLaunchKernelGGL(chol_update_kernel<MODE>, dim3(update_grid(nt, batch), batch),
+                         dim3(256), 0, stream, p.A, p.lda, p.sA, p.X, p.ldx, p.sX, p.n, k, T,
+                         p.info, p.logdet);
       GP_CK(hipGetLastError());
     }
     if (ev && (k == k_ev || (k == N - 1 && k_ev >= N))) GP_CK(hipEventRecord(ev, stream));
@@ -2150,18 +2093,6 @@ static int potrf_sweep(double* A, int n, int lda, long long sA, double* X, int l
 // gp_set_potrf_path (test / A-B hook): 1 forces the blocked sweep for later factorisations,
 // 2 the persistent kernel with one shared queue for every batch
 static int g_potrf_path = 0;
-
-static int num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
 
 // pp_kernel workgroups that can be resident at once on `stream`: its occupancy (1 per CU) x
 // the CUs the stream's CU mask enables.  The dequeue lead and the eligibility test are bounded
@@ -2175,7 +2106,7 @@ static int pp_resident(hipStream_t stream) {
       o = 1;
     return o;
   }();
-  int cus = num_cus();
+  int cus = gp_num_cus();
   std::vector<uint32_t> mask((cus + 31) / 32, 0u);
   if (hipExtStreamGetCUMask(stream, (uint32_t)mask.size(), mask.data()) == hipSuccess) {
     int on = 0;
@@ -2220,9 +2151,9 @@ static PPScratch pp_scratch(int n, int batch, bool inv) {
   PPScratch s;
   const int N = gp_ceil_div(n, NB);
   s.ntasks = pp_task_count(N, inv) * batch;
-  s.fstride = ((2 * N * N + 2 * N + 1 + 31) / 32) * 32;   // FL, FX, DPF, SPF, abort
-  s.task_bytes = ((size_t)s.ntasks * sizeof(int2) + 255) / 256 * 256;
-  s.flag_bytes = ((256 + (size_t)batch * s.fstride * sizeof(int)) + 255) / 256 * 256;
+  s.fstride = ((PPFlags::words(N) + 31) / 32) * 32;
+  s.task_bytes = (size_t)align256(s.ntasks * (long long)sizeof(int2));
+  s.flag_bytes = (size_t)align256(256 + (long long)batch * s.fstride * (long long)sizeof(int));
   return s;
 }
 
@@ -2231,7 +2162,6 @@ static bool pp_shape_ok(int n, int batch) {
   return N <= kPPMaxN && pp_task_count(N, true) * (long long)batch < (1ll << 30);
 }
 
-
 static bool pp_eligible(int n, int batch, int resident) {
   // the chains hold `batch` workgroups for the whole launch: at least as many workers again
   return g_potrf_path != 1 && pp_shape_ok(n, batch) && 2 * batch <= resident;
@@ -2239,19 +2169,12 @@ static bool pp_eligible(int n, int batch, int resident) {
 
 // The persistent dataflow factorisation (pp_kernel) on `stream` in the caller's scratch `scr`
 // (pp_scratch bytes, 256-B aligned): one schedule launch, one persistent launch with one
-// workgroup per resident slot.  X is L^-1 (inv, zeroed by the caller) or the 64 x 64N D_k
-// scratch (ldx = 64).
-// gp_loglik's in-chain mode (gpfit_potrf_loglik): pp_kernel<true> with these PPArgs fields
-struct PPLL {
-  const double* w; int ldw;
-  double* zb; int zld, zq_off;
-  double* zz; double* ll; int* status; int* info_out;
-};
-
-static int pp_factor(double* A, int n, int lda, long long sA, double* X, int ldx, long long sX,
-                     int batch, int* info, double* logdet, bool inv, char* scr, int resident,
-                     hipStream_t stream, GpfitPre pre = GpfitPre(),
-                     hipEvent_t ev_launch = nullptr, const PPLL* ll = nullptr) {
+// workgroup per resident slot.  p.X is L^-1 (inv, zeroed by the caller) or the 64 x 64N D_k
+// scratch (ldx = 64).  `ll`: gp_loglik's in-chain mode (gpfit_potrf_loglik), pp_kernel<true>.
+static int pp_factor(const Problem& p, bool inv, char* scr, int resident, hipStream_t stream,
+                     GpfitPre pre = GpfitPre(), hipEvent_t ev_launch = nullptr,
+                     const PPLoglik* ll = nullptr) {
+  const int n = p.n, batch = p.batch;
   const int N = gp_ceil_div(n, NB);
   const PPScratch s = pp_scratch(n, batch, inv);
   const int grid = (int)(s.ntasks < resident ? s.ntasks : resident);
@@ -2263,7 +2186,7 @@ static int pp_factor(double* A, int n, int lda, long long sA, double* X, int ldx
   // the schedule kernel also zeroes head + flags and info / logdet
   hipLaunchKernelGGL(pp_schedule_kernel, dim3(pp_schedule_grid(batch)), dim3(1024), 0, stream,
                      tasks, N, batch, inv ? 1 : 0, lead, kPPXDelay, head, 256 / (int)sizeof(int),
-                     info, logdet, flags, s.fstride, budget < 0 ? 1 : 0);
+                     p.info, p.logdet, flags, s.fstride, budget < 0 ? 1 : 0);
   GP_CK(hipGetLastError());
   if (pre.fn) {
     const int prc = pre.fn(pre.arg);
@@ -2271,15 +2194,15 @@ static int pp_factor(double* A, int n, int lda, long long sA, double* X, int ldx
   }
   if (ev_launch) GP_CK(hipEventRecord(ev_launch, stream));   // after the Gram, before pp_kernel
   PPArgs P;
-  P.A = A; P.sA = sA; P.lda = lda;
-  P.X = X; P.sX = sX; P.ldx = ldx;
+  P.A = p.A; P.sA = p.sA; P.lda = p.lda;
+  P.X = p.X; P.sX = p.sX; P.ldx = p.ldx;
   P.n = n; P.N = N; P.batch = batch; P.inv = inv ? 1 : 0;
+  P.info = p.info; P.logdet = p.logdet;
   // plain (L2-cached) loads of produced tiles only when no 128-B line spans two tiles
-  auto al128 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 127) == 0; };
-  P.plain = (lda % 16 == 0) && (ldx % 16 == 0) && al128(A) && al128(X) &&
-            (batch == 1 || (sA % 16 == 0 && sX % 16 == 0));
+  auto al128 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 127) == 0; };
+  P.plain = (p.lda % 16 == 0) && (p.ldx % 16 == 0) && al128(p.A) && al128(p.X) &&
+            (batch == 1 || (p.sA % 16 == 0 && p.sX % 16 == 0));
   P.budget = budget > 0 ? budget : kPollBudget;
-  P.info = info; P.logdet = logdet;
   P.tasks = tasks; P.ntasks = (int)s.ntasks;
   P.groups = pp_groups(batch, grid);
   P.head = head; P.flags = flags; P.fstride = s.fstride;
@@ -2287,15 +2210,9 @@ static int pp_factor(double* A, int n, int lda, long long sA, double* X, int ldx
   P.dbg = g_trace_dbg;
   P.trace = g_trace_buf;
 #endif
-  P.w = nullptr; P.ldw = 0; P.zb = nullptr; P.zld = 0; P.zq_off = 0;
-  P.zz = nullptr; P.ll = nullptr; P.status = nullptr; P.info_out = nullptr;
-  if (ll) {
-    P.w = ll->w; P.ldw = ll->ldw; P.zb = ll->zb; P.zld = ll->zld; P.zq_off = ll->zq_off;
-    P.zz = ll->zz; P.ll = ll->ll; P.status = ll->status; P.info_out = ll->info_out;
-    hipLaunchKernelGGL(pp_kernel<true>, dim3(grid), dim3(256), 0, stream, P);
-  } else {
-    hipLaunchKernelGGL(pp_kernel<false>, dim3(grid), dim3(256), 0, stream, P);
-  }
+  P.lik = ll ? *ll : PPLoglik{};
+  if (ll) hipLaunchKernelGGL(pp_kernel<true>, dim3(grid), dim3(256), 0, stream, P);
+  else hipLaunchKernelGGL(pp_kernel<false>, dim3(grid), dim3(256), 0, stream, P);
   GP_CK(hipGetLastError());
   return 0;
 }
@@ -2327,14 +2244,21 @@ extern "C" long long gp_potrf_inv_ws_bytes(int n, int batch) {
   return gpfit_potrf_inv_ws_bytes(n, batch);
 }
 
+// gp_potrf's D_k scratch: NB x (N NB) doubles per problem (potrf_d_stride), at the head of its
+// workspace
+static long long potrf_d_stride(int n) { return (long long)NB * gp_ceil_div(n, NB) * NB; }
+static long long potrf_d_bytes(int n, int batch) {
+  return align256(8LL * potrf_d_stride(n) * batch);
+}
+
 extern "C" long long gp_potrf_ws_bytes(int n, int batch) {
   if (n < 0 || batch < 0) return -1;
   if (n == 0 || batch == 0) return 0;
-  const long long sD = (long long)NB * gp_ceil_div(n, NB) * NB;
-  const long long d = ((8LL * sD * batch) + 255) / 256 * 256;
-  return d + (pp_shape_ok(n, batch) ? (long long)pp_scratch(n, batch, false).bytes() : 0);
+  return potrf_d_bytes(n, batch) +
+         (pp_shape_ok(n, batch) ? (long long)pp_scratch(n, batch, false).bytes() : 0);
 }
 
+// Codes -1 .. -8 of gp_potrf_inv / gp_potrf_inv_ws / gp_trtri (A is gp_trtri's L).
 static int potrf_inv_args(const double* A, int n, int lda, long long strideA, const double* Linv,
                           int ldinv, long long strideInv, int batch) {
   if (!A) return -1;
@@ -2365,6 +2289,7 @@ int gpfit_potrf_inv_event(double* A, int n, int lda, long long strideA, double* 
   const int arc = potrf_inv_args(A, n, lda, strideA, Linv, ldinv, strideInv, batch);
   if (arc) return arc;
   if (n == 0 || batch == 0) return pre.fn ? pre.fn(pre.arg) : 0;
+  const Problem p{A, lda, strideA, Linv, ldinv, strideInv, n, batch, info, logdet};
   const int npad = gp_padded_n(n);
   const int resident = pp_resident(stream);
   const bool pp = pp_eligible(n, batch, resident);
@@ -2389,13 +2314,11 @@ int gpfit_potrf_inv_event(double* A, int n, int lda, long long strideA, double* 
     // waits on it runs beside the whole factorisation, not beside the Gram),
     // one asked for at k_ev >= N after it
     const int N = gp_ceil_div(n, NB);
-    rc = pp_factor(A, n, lda, strideA, Linv, ldinv, strideInv, batch, info, logdet, true,
-                   static_cast<char*>(ws), resident, stream, pre,
+    rc = pp_factor(p, true, static_cast<char*>(ws), resident, stream, pre,
                    (ev && k_ev >= 0 && k_ev < N) ? ev : nullptr);
     if (rc == 0 && ev && !(k_ev >= 0 && k_ev < N)) GP_CK(hipEventRecord(ev, stream));
   } else {
-    rc = potrf_sweep<kPotrfInv>(A, n, lda, strideA, Linv, ldinv, strideInv, batch, info, logdet,
-                                stream, k_ev, ev);
+    rc = potrf_sweep<kPotrfInv>(p, stream, k_ev, ev);
   }
   gpfit_prof_end(GP_PROF_POTRF, stream);
   return rc;
@@ -2416,12 +2339,12 @@ int gpfit_potrf_loglik(double* G, int n, long long strideG, double* D, long long
   if (ws_bytes < gpfit_potrf_loglik_ws_bytes(n, batch)) return -12;
   const int N = gp_ceil_div(n, NB);
   if (strideD < (long long)NB * NB * N || zld < 2 * NB * N) return -13;
-  PPLL L{w, ldw, zb, zld, NB * N, zz, ll, status, info_out};
+  const PPLoglik L{w, ldw, zb, zld, NB * N, zz, ll, status, info_out};
+  const Problem p{G, n, strideG, D, NB, strideD, n, batch, info, logdet};
   // (the profiler's POTRF pair brackets the Gram `pre` too on this path: it is enqueued
   // between the schedule kernel and pp_kernel; the fit's roofline subtracts nothing for it)
   gpfit_prof_begin(GP_PROF_POTRF, stream);
-  const int rc = pp_factor(G, n, n, strideG, D, NB, strideD, batch, info, logdet, false,
-                           static_cast<char*>(ws), resident, stream, pre, nullptr, &L);
+  const int rc = pp_factor(p, false, static_cast<char*>(ws), resident, stream, pre, nullptr, &L);
   gpfit_prof_end(GP_PROF_POTRF, stream);
   return rc;
 }
@@ -2434,23 +2357,30 @@ extern "C" int gp_potrf_inv_ws(double* A, int n, int lda, long long strideA, dou
                                ws, ws_bytes, stream, -1, nullptr);
 }
 
-// The allocating forms: stream-ordered scratch (hipMallocAsync), freed behind the launches on
-// every path, including a failed launch.
+// The allocating forms: fn(ws) with `bytes` of stream-ordered scratch (hipMallocAsync), freed
+// behind the launches on every path, including a failed launch.
+template <typename F>
+static int with_stream_scratch(long long bytes, hipStream_t stream, F&& fn) {
+  void* ws = nullptr;
+  if (bytes > 0) GP_CK(hipMallocAsync(&ws, (size_t)bytes, stream));
+  const int rc = fn(ws);
+  if (ws) {
+    const hipError_t e = hipFreeAsync(ws, stream);
+    if (rc == 0 && e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
+  }
+  return rc;
+}
+
 extern "C" int gp_potrf_inv(double* A, int n, int lda, long long strideA, double* Linv,
                             int ldinv, long long strideInv, int batch, int* info,
                             double* logdet, hipStream_t stream) {
   const int arc = potrf_inv_args(A, n, lda, strideA, Linv, ldinv, strideInv, batch);
   if (arc) return arc;
   const long long bytes = (n > 0 && batch > 0) ? gpfit_potrf_inv_ws_bytes(n, batch) : 0;
-  void* ws = nullptr;
-  if (bytes > 0) GP_CK(hipMallocAsync(&ws, (size_t)bytes, stream));
-  const int rc = gp_potrf_inv_ws(A, n, lda, strideA, Linv, ldinv, strideInv, batch, info,
-                                 logdet, ws, bytes, stream);
-  if (ws) {
-    const hipError_t e = hipFreeAsync(ws, stream);
-    if (rc == 0 && e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
-  }
-  return rc;
+  return with_stream_scratch(bytes, stream, [&](void* ws) {
+    return gp_potrf_inv_ws(A, n, lda, strideA, Linv, ldinv, strideInv, batch, info, logdet, ws,
+                           bytes, stream);
+  });
 }
 
 extern "C" int gp_potrf_ws(double* A, int n, int lda, long long strideA, int batch, int* info,
@@ -2466,15 +2396,12 @@ extern "C" int gp_potrf_ws(double* A, int n, int lda, long long strideA, int bat
     if (info) GP_CK(hipMemsetAsync(info, 0, sizeof(int) * batch, stream));
     if (logdet) GP_CK(hipMemsetAsync(logdet, 0, sizeof(double) * batch, stream));
   }
-  // D_k scratch: NB x (N NB) per problem at the head of ws, then the persistent scratch
-  const int N = gp_ceil_div(n, NB);
-  const long long sD = (long long)NB * N * NB;
-  double* D = static_cast<double*>(ws);
-  char* scr = static_cast<char*>(ws) + ((8LL * sD * batch) + 255) / 256 * 256;
-  return pp ? pp_factor(A, n, lda, strideA, D, NB, sD, batch, info, logdet, false, scr, resident,
-                        stream)
-            : potrf_sweep<kPotrf>(A, n, lda, strideA, D, NB, sD, batch, info, logdet, stream,
-                                  -1, nullptr);
+  // the D_k scratch at the head of ws, then the persistent scratch
+  const Problem p{A, lda, strideA, static_cast<double*>(ws), NB, potrf_d_stride(n), n, batch,
+                  info, logdet};
+  char* scr = static_cast<char*>(ws) + potrf_d_bytes(n, batch);
+  return pp ? pp_factor(p, false, scr, resident, stream)
+            : potrf_sweep<kPotrf>(p, stream, -1, nullptr);
 }
 
 extern "C" int gp_potrf(double* A, int n, int lda, long long strideA, int batch, int* info,
@@ -2482,29 +2409,20 @@ extern "C" int gp_potrf(double* A, int n, int lda, long long strideA, int batch,
   const int arc = potrf_args(A, n, lda, strideA, batch);
   if (arc) return arc;
   const long long bytes = (n > 0 && batch > 0) ? gp_potrf_ws_bytes(n, batch) : 0;
-  void* ws = nullptr;
-  if (bytes > 0) GP_CK(hipMallocAsync(&ws, (size_t)bytes, stream));
-  const int rc = gp_potrf_ws(A, n, lda, strideA, batch, info, logdet, ws, bytes, stream);
-  if (ws) {
-    const hipError_t e = hipFreeAsync(ws, stream);
-    if (rc == 0 && e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
-  }
-  return rc;
+  return with_stream_scratch(bytes, stream, [&](void* ws) {
+    return gp_potrf_ws(A, n, lda, strideA, batch, info, logdet, ws, bytes, stream);
+  });
 }
 
 extern "C" int gp_trtri(const double* L, int n, int ldl, long long strideL, double* Linv,
                         int ldinv, long long strideInv, int batch, int* info,
                         hipStream_t stream) {
-  if (!L) return -1;
-  if (n < 0) return -2;
-  if (ldl < n || ldl < 1) return -3;
-  if (batch > 1 && strideL < (long long)ldl * n) return -4;
-  if (!Linv) return -5;
-  const int npad = gp_padded_n(n);
-  if (ldinv < npad || ldinv < 1) return -6;
-  if (batch > 1 && strideInv < (long long)ldinv * npad) return -7;
-  if (batch < 0) return -8;
+  const int arc = potrf_inv_args(L, n, ldl, strideL, Linv, ldinv, strideInv, batch);
+  if (arc) return arc;
   if (n == 0 || batch == 0) return 0;
+  const int npad = gp_padded_n(n);
+  const Problem p{const_cast<double*>(L), ldl, strideL, Linv, ldinv, strideInv, n, batch, info,
+                  nullptr};
   // trtri_diag_kernel lowers info[b] (atomicMin) from a "none" sentinel; the sweep's kernels
   // then skip every problem with info != 0
   if (info) GP_CK(hipMemsetAsync(info, 0x7f, sizeof(int) * batch, stream));
@@ -2517,8 +2435,7 @@ extern "C" int gp_trtri(const double* L, int n, int ldl, long long strideL, doub
                        info, batch);
     GP_CK(hipGetLastError());
   }
-  return potrf_sweep<kTrtri>(const_cast<double*>(L), n, ldl, strideL, Linv, ldinv, strideInv,
-                             batch, info, nullptr, stream, -1, nullptr);
+  return potrf_sweep<kTrtri>(p, stream, -1, nullptr);
 }
 
 // Poll budget of the persistent factorisation's waits for later launches (process-wide test /
@@ -2552,4 +2469,3 @@ extern "C" long long gp_pp_trace_slots(int n, int batch) {
   return pp_scratch(n, batch, true).ntasks * kPPTraceSlots + (long long)batch * N * 8;
 }
 #endif
-#undef GP_CK

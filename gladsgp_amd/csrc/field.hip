@@ -242,18 +242,6 @@ __global__ __launch_bounds__(kFieldThreads, FIELD_OCC) void field_kernel(const d
   }
 }
 
-int field_num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
-
 template <int KS, bool F32>
 hipError_t launch_field(const double* W, long long ldw, int rows, int P, const double* K,
                         long long ldk, int ncols, const double* sd, const double* mu,
@@ -262,7 +250,7 @@ hipError_t launch_field(const double* W, long long ldw, int rows, int P, const d
   constexpr int kFieldRows = field_rows<KS>();
   const long long ntiles = ((long long)rows + kFieldRows - 1) / kFieldRows;
   // one residency round: FIELD_OCC waves per SIMD (launch_bounds' second argument), 4 SIMDs
-  long long blocks = (long long)field_num_cus() *
+  long long blocks = (long long)gp_num_cus() *
                      (FIELD_OCC * 4 >= kFieldWaves ? FIELD_OCC * 4 / kFieldWaves : 1);
   if (blocks > npanels * ntiles) blocks = npanels * ntiles;
   // 16-B stores need 16-B aligned rows

@@ -196,3 +196,27 @@ GP_DEV int xcd_remap(int b, int nwg) {
 }
 
 __host__ __device__ inline int gp_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- Host helpers shared by the entry points --------------------------------------------------
+constexpr long long align256(long long bytes) { return ((bytes + 255) / 256) * 256; }
+
+// in an entry point: a HIP error ends the call with its C-ABI code (include/gpfit.h)
+#define GP_CK(x)                                            \
+  do {                                                      \
+    const hipError_t e_ = (x);                              \
+    if (e_ != hipSuccess) return GPFIT_ERR_HIP - (int)e_;   \
+  } while (0)
+
+// Compute units of the current device, queried once per process (256, MI355X's, if the query
+// fails): the launch grids that are capped at the resident workgroups are sized by it.
+inline int gp_num_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+    return n;
+  }();
+  return ncu;
+}

@@ -170,18 +170,6 @@ int ardse_blocks_per_cu() {
   return occ;
 }
 
-int gram_num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
-
 template <int D>
 hipError_t launch_ardse(const double* XA, int na, int ldxa, const double* XB, int nb, int ldxb,
                         int d, const double* beta, int ldbeta, const double* s,
@@ -198,7 +186,7 @@ hipError_t launch_ardse(const double* XA, int na, int ldxa, const double* XB, in
   g.units = (int)(tiles * kTile);
   // one residency round: every wave of the grid is resident at once (or the grid is smaller
   // than that, when there are fewer than ~8 units per wave)
-  const long long cap = (long long)gram_num_cus() * ardse_blocks_per_cu<D>();
+  const long long cap = (long long)gp_num_cus() * ardse_blocks_per_cu<D>();
   const long long want = gp_ceil_div(total, 8LL * kWaves);
   const int grid = (int)(want < cap ? want : cap);
   hipLaunchKernelGGL((ardse_kernel<D>), dim3(grid), dim3(256), 0, st, XA, na, ldxa, XB, nb, ldxb,

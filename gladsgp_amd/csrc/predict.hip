@@ -35,15 +35,6 @@ constexpr long long kDefaultChunkElems = 256ll << 20;  // <= 2 GB of Kt per chun
 constexpr int kDefaultChunk = 8192;                   // test points per chunk (batches)
 constexpr int kDefaultChunkSingle = 16384;            // ... and for one GP
 
-constexpr long long align256(long long bytes) { return ((bytes + 255) / 256) * 256; }
-
-// in an entry point: a HIP error ends the call with its C-ABI code
-#define GP_CK(x)                                            \
-  do {                                                      \
-    const hipError_t e_ = (x);                              \
-    if (e_ != hipSuccess) return GPFIT_ERR_HIP - (int)e_;   \
-  } while (0)
-
 // Cross-covariance chunk, k-major as the TRMM streams it:
 //   Kt[k * mc + c] = s * exp(-sum beta (X[k] - Xs[c])^2)
 // (exp by the 64-entry table, exp_neg_tab: the kernel is bound by its fp64 VALU work)
@@ -1044,15 +1035,14 @@ int trmm_slots() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   int v = cache[dev].load(std::memory_order_relaxed);
   if (v > 0) return v;
-  int ncu = 0, nb = 0;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      ncu < 1)
-    ncu = 256;
+  int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trmm_pair_kernel<false>, 256, 0) !=
           hipSuccess ||
       nb < 1)
     nb = 2;
-  v = ncu * nb;
+  // (gp_num_cus is the CU count of the device current at the library's first query: a process
+  // that mixes devices of different sizes gets that count for all of them)
+  v = gp_num_cus() * nb;
   cache[dev].store(v, std::memory_order_relaxed);
   return v;
 }

@@ -294,18 +294,6 @@ __global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kern
   }
 }
 
-int summary_num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
-
 struct SumArgs {
   const double* W;
   long long ldw, lds;
@@ -339,7 +327,7 @@ hipError_t launch_summary(const SumArgs& a) {
   const long long units = (long long)gp_ceil_div(a.ncols, kSumCols) * a.m;
   const int nts = (a.S + sum_rows<KS>() - 1) / sum_rows<KS>();
   // one residency round: no tail round of blocks
-  long long blocks = (long long)summary_num_cus() * summary_blocks_per_cu<KS, KT>();
+  long long blocks = (long long)gp_num_cus() * summary_blocks_per_cu<KS, KT>();
   if (blocks > units) blocks = units;
   hipLaunchKernelGGL((summary_kernel<KS, KT>), dim3((unsigned)blocks), dim3(kSumThreads), 0,
                      a.stream, a.W, a.ldw, a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu,

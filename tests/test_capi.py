@@ -341,6 +341,111 @@ def test_prediction_return_codes(lib, table):
         (change, want, g) for (change, want), g in zip(rows, got) if g != want]
 
 
+# Return codes of the factorisation entry points, in the same form.  No row may reach an
+# allocation or a launch (the pointers are dummies): the bases of the allocating forms and of
+# gp_trtri have n = 0 (a valid no-op, where one changed field still reaches every code), those
+# of the _ws forms a workspace that is too small.  Rows change one field; the few with two
+# faults pin the order of the checks.
+_FACT = dict(A=_P, n=0, lda=1, strideA=0, batch=2, info=None, stream=None)
+_FACT_INV = dict(_FACT, Linv=_P, ldinv=1, strideInv=0)
+_FACT_N = dict(n=_N, lda=_N, strideA=_N * _N)
+_INV_ORDER = ["A", "n", "lda", "strideA", "Linv", "ldinv", "strideInv", "batch", "info"]
+
+
+def _rows_fact(batch_rc):
+    """potrf_args' codes (the plain forms), shared by the inverse forms up to the batch."""
+    return [(dict(A=None), -1), (dict(n=-1), -2), (dict(lda=0), -3), (dict(strideA=-1), -4),
+            (dict(batch=-1), batch_rc), (dict(batch=0), 0),
+            (dict(strideA=-1, batch=1), 0),                 # one problem: no stride to check
+            (dict(A=None, n=-1), -1), (dict(n=-1, lda=0), -2), (dict(lda=0, strideA=-1), -3)]
+
+
+def _rows_fact_inv():
+    return _rows_fact(-8) + [
+        (dict(Linv=None), -5), (dict(ldinv=0), -6), (dict(strideInv=-1), -7),
+        (dict(strideInv=-1, batch=1), 0),
+        (dict(strideA=-1, Linv=None), -4), (dict(Linv=None, ldinv=0), -5),
+        (dict(ldinv=0, strideInv=-1), -6), (dict(ldinv=0, batch=-1), -6)]
+
+
+# the same codes at n > 0 (every row still fails validation)
+_ROWS_FACT_N = [(dict(A=None), -1), (dict(n=-1), -2), (dict(lda=_N - 1), -3),
+                (dict(strideA=_N * _N - 1), -4)]
+_ROWS_FACT_INV_N = _ROWS_FACT_N + [
+    (dict(Linv=None), -5), (dict(ldinv=_NPAD - 1), -6), (dict(ldinv=64), -6),
+    (dict(strideInv=_NPAD * _NPAD - 1), -7), (dict(batch=-1), -8), (dict(batch=0), 0),
+    (dict(n=0), 0)]
+
+
+def _potrf_inv_table():
+    order = _INV_ORDER + ["logdet", "stream"]
+    return "gp_potrf_inv", order, dict(_FACT_INV, logdet=None), 0, _rows_fact_inv()
+
+
+def _potrf_inv_ws_table():
+    order = _INV_ORDER + ["logdet", "ws", "ws_bytes", "stream"]
+    base = dict(_FACT_INV, **_FACT_N, ldinv=_NPAD, strideInv=_NPAD * _NPAD, logdet=None,
+                ws=256, ws_bytes=16)
+    rows = _ROWS_FACT_INV_N + [
+        (dict(ws=None), -11), (dict(ws=16), -11),           # workspace not 256-B aligned
+        (dict(ws=None, ws_bytes=1 << 40), -11), (dict(ws=None, Linv=None), -5),
+        (dict(ws_bytes=0), -12), (dict(ws_bytes=16, batch=-1), -8)]
+    return "gp_potrf_inv_ws", order, base, -12, rows
+
+
+def _potrf_table():
+    order = ["A", "n", "lda", "strideA", "batch", "info", "logdet", "stream"]
+    return "gp_potrf", order, dict(_FACT, logdet=None), 0, _rows_fact(-5)
+
+
+def _potrf_ws_table():
+    order = ["A", "n", "lda", "strideA", "batch", "info", "logdet", "ws", "ws_bytes", "stream"]
+    base = dict(_FACT, **_FACT_N, logdet=None, ws=256, ws_bytes=16)
+    rows = _ROWS_FACT_N + [
+        (dict(batch=-1), -5), (dict(batch=0), 0), (dict(n=0), 0),
+        (dict(ws=None), -8), (dict(ws=16), -8), (dict(ws=None, ws_bytes=1 << 40), -8),
+        (dict(ws=None, A=None), -1), (dict(ws=None, n=0), 0),     # the no-op needs no scratch
+        (dict(ws_bytes=0), -9), (dict(ws_bytes=16, batch=-1), -5)]
+    return "gp_potrf_ws", order, base, -9, rows
+
+
+def _trtri_table():
+    ren = {"A": "L", "lda": "ldl", "strideA": "strideL"}
+    order = [ren.get(k, k) for k in _INV_ORDER] + ["stream"]
+    base = {ren.get(k, k): v for k, v in _FACT_INV.items()}
+    rows = [({ren.get(k, k): v for k, v in change.items()}, rc)
+            for change, rc in _rows_fact_inv()]
+    return "gp_trtri", order, base, 0, rows
+
+
+@pytest.mark.parametrize("table", [_potrf_inv_table, _potrf_inv_ws_table, _potrf_table,
+                                   _potrf_ws_table, _trtri_table],
+                         ids=lambda t: t.__name__.strip("_"))
+def test_factorisation_return_codes(lib, table):
+    """gp_potrf_inv / _ws, gp_potrf / _ws and gp_trtri: which argument is reported, and in
+    which order, before anything is allocated or enqueued."""
+    name, order, base, base_rc, rows = table()
+    assert sorted(order) == sorted(base), name
+    rows = [({}, base_rc)] + rows
+    codes = {"gp_potrf": {-1, -2, -3, -4, -5}, "gp_potrf_ws": {-1, -2, -3, -4, -5, -8, -9},
+             "gp_potrf_inv_ws": set(range(-8, 0)) | {-11, -12}}.get(name, set(range(-8, 0)))
+    assert {rc for _, rc in rows if rc} == codes, name      # every documented code appears
+    fn = getattr(lib, name)
+    prev = lib.gp_set_potrf_path(0)     # -11 / -12 are the persistent factorisation's scratch
+    try:
+        got = []
+        for change, rc in rows:
+            assert set(change) <= set(base), (name, change)
+            args = dict(base, **change)
+            # a row that passed validation would allocate or launch on the dummy pointers
+            assert rc < 0 or args["n"] == 0 or args["batch"] == 0, (name, change)
+            got.append(fn(*[args[k] for k in order]))
+    finally:
+        lib.gp_set_potrf_path(prev)
+    assert got == [rc for _, rc in rows], [
+        (change, rc, g) for (change, rc), g in zip(rows, got) if g != rc]
+
+
 def test_required_alignment_return_codes(lib):
     """The operands whose alignment the header requires (include/gpfit.h, layout contract): a
     16-B aligned L^-1 / packed P with an even ldinv and strideInv, a 256-B aligned workspace.

@@ -1,8 +1,9 @@
 // Microbenchmark (debug only): the 16 x 16 leaf of the chain's diagonal factor, cycles per
-// variant on one workgroup (build like diag_micro.hip): leaf16 (one wave: A and W MFMAs), leaf16_elim alone (wave 0, the
-// W handoff unused), leaf16_elim + leaf16_inv (waves 0 and 1), and the elimination without the
+// variant on one workgroup (build like diag_micro.hip): leaf16 (tools/dbg/leaf16.h, one wave:
+// A and W MFMAs), leaf16_elim alone (wave 0, the W handoff unused), leaf16_elim + leaf16_inv (waves 0 and 1), and the elimination without the
 // multiplier stores / step releases.
 #include "../../gladsgp_amd/csrc/chol.hip"
+#include "leaf16.h"
 #include <cstdio>
 #include <vector>
 
@@ -19,10 +20,10 @@
 //    lane j+1 uses), so step j+1 needs only A (MFMA -> VALU -> MFMA: multiplier = row * r) and
 //    an r already in an SGPR pair.  Every pivot (L's diagonal and column scales, the checks, the
 //    log) is that recurrence value.  The multipliers go to LDS (one 8-B slot per lane and step)
-//    and a step counter is released every DIAG_PE steps;
+//    and a step counter is released every kDiagPublishEvery steps;
 //  * wave 1 (leaf16_inv) replays W = Lt^-1 from the published multipliers (the identical
-//    W MFMA sequence of leaf16) on its own SIMD's matrix pipe, trailing wave 0 by < DIAG_PE
-//    steps, then scales W's rows by the pivots wave 0 publishes last.
+//    W MFMA sequence of leaf16) on its own SIMD's matrix pipe, trailing wave 0 by fewer than
+//    kDiagPublishEvery steps, then scales W's rows by the pivots wave 0 publishes last.
 // Same arithmetic as leaf16 operation for operation where the f64 MFMA's single product
 // accumulates exactly (fused, one rounding): bit-identical L and L^-1 then.
 using lds_int = __attribute__((address_space(3))) int;
@@ -53,7 +54,7 @@ GP_DEV void leaf16_elim(lds_double* T, int o, lds_double* piv, lds_double* M, ld
       M[j * 64 + lane] = m;
       // release the multipliers of the previous group: their stores went out a step ago, so
       // the release's lgkmcnt(0) wait finds them done
-      if constexpr (j % DIAG_PE == 0 && j > 0)
+      if constexpr (j % kDiagPublishEvery == 0 && j > 0)
         __hip_atomic_store(step, base + j, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       const double b = readlane_f64(rowj, 16 * k + j + 1);        // A[j][j+1]
       const double dd = readlane_f64(dg, 16 * k1 + j + 1);        // A[j+1][j+1]
@@ -83,8 +84,8 @@ GP_DEV void leaf16_inv(lds_double* U, int o, const lds_double* piv, const lds_do
   static_for<0, 15, 1>([&](auto J) {
     constexpr int j = decltype(J)::value;
     constexpr int q = j >> 2;
-    if constexpr (j % DIAG_PE == 0)
-      lds_wait_ge((int*)step, base + ((j + DIAG_PE < 15) ? j + DIAG_PE : 15));
+    if constexpr (j % kDiagPublishEvery == 0)
+      lds_wait_ge((int*)step, base + ((j + kDiagPublishEvery < 15) ? j + kDiagPublishEvery : 15));
     const double m = M[j * 64 + lane];
     const double wj = W[q];
     W = mfma16x16x4(-m, wj, W);

@@ -1,7 +1,8 @@
 // Microbenchmark (debug only): where the cycles of the chain's 16 x 16 leaf go.  A copy of
-// chol.hip's leaf16 with s_memtime stamps between its phases (load, elimination, rsqrt,
+// leaf16 (tools/dbg/leaf16.h, once chol.hip's leaf) with s_memtime stamps between its phases (load, elimination, rsqrt,
 // stores, pivot check + log), run by one wave on one workgroup.
 #include "../../gladsgp_amd/csrc/chol.hip"
+#include "leaf16.h"
 #include <cstdio>
 #include <vector>
 

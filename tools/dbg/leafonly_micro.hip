@@ -3,6 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form \
 //     -Xclang -target-feature -Xclang +enable-ds128 tools/dbg/leafonly_micro.hip -o ...
 #include "../../gladsgp_amd/csrc/chol.hip"
+#include "leaf16.h"
 #include <cstdio>
 #include <vector>
 
