@@ -115,6 +115,12 @@ SIGNATURES = {
     "gp_field_summary": (c_int, [c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_void_p, c_ll, c_int,
                                  c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
                                  c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
+    "gp_field_score_ws_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "gp_field_score": (c_int, [c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_void_p, c_ll, c_int,
+                               c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
+                               c_void_p, c_ll, c_int, ctypes.c_double, c_void_p, c_void_p,
+                               c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_ll,
+                               c_void_p]),
     "gp_sobol_replicates": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_int,
                                     c_int, c_void_p, c_ll, c_int, c_int, ctypes.c_ulonglong,
                                     ctypes.c_ulonglong, c_void_p, c_int, c_void_p, c_void_p,
@@ -148,6 +154,10 @@ SIGNATURES = {
 
 PROF_GRAM, PROF_POTRF, PROF_TRMM, PROF_CROSS = 0, 1, 2, 3
 LINV_PADDED, LINV_PACKED = 0, 1        # GPFIT_LINV_PADDED / GPFIT_LINV_PACKED
+# GPFIT_SCORE_ROW_* / GPFIT_SCORE_COL_*: the columns of gp_field_score's rows and cols
+SCORE_ROW = {"sqerr": 0, "valid": 1, "ape": 2, "ape_n": 3, "lo": 4, "hi": 5, "covered": 6,
+             "mean": 7}
+SCORE_COL = {"sqerr": 0, "valid": 1, "covered": 2, "width": 3}
 
 
 class GPFitUnavailable(RuntimeError):

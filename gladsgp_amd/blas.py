@@ -175,6 +175,67 @@ def _band(q):
     return float(q_lo), float(q_hi)
 
 
+def _summary_operands(fn, W3, K, sd, mu, err, q):
+    """The operand checks field_summary and field_score share -> (S, m, P, ncols, ldw, lds, ldk,
+    q_lo, q_hi); every refusal is a ValueError that names ``fn``."""
+    for nm, t, nd in (("W3", W3, 3), ("K", K, 2)):
+        if not torch.is_tensor(t) or t.dtype != F64 or t.dim() != nd:
+            raise ValueError(f"{fn}: {nm} must be a {nd}-d float64 tensor")
+    S, m, P = W3.shape
+    dev = W3.device
+    if K.device != dev:
+        raise ValueError(f"{fn}: W3 and K must be on one device")
+    if S < 1 or P < 1 or K.shape[0] != P:
+        raise ValueError(f"{fn}: W3 {tuple(W3.shape)} needs S >= 1 samples and K "
+                         f"{tuple(K.shape)} one row per PC")
+    ncols = K.shape[1]
+    ldw = W3.stride(1) if m > 1 else max(W3.stride(1), P)
+    lds = W3.stride(0) if S > 1 else max(W3.stride(0), (m - 1) * ldw + P)
+    if (P > 1 and W3.stride(2) != 1) or ldw < P or lds < (max(m, 1) - 1) * ldw + P:
+        raise ValueError(f"{fn}: W3 needs a unit last stride and sample-major strides "
+                         f"(lds >= (m - 1) ldw + P, ldw >= P), got {W3.stride()}")
+    ldk = K.stride(0) if P > 1 else max(K.stride(0), ncols, 1)
+    if (ncols > 1 and K.stride(1) != 1) or ldk < max(ncols, 1):
+        raise ValueError(f"{fn}: K must be row-major (strides {K.stride()})")
+    if (sd is None) != (mu is None):
+        raise ValueError(f"{fn}: sd and mu go together")
+    for nm, t, n in (("sd", sd, ncols), ("mu", mu, ncols), ("err", err, S * m)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != F64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fn}: {nm} must be contiguous float64 on W3's device")
+        if t.numel() != n:
+            raise ValueError(f"{fn}: {nm} has {t.numel()} values, expected {n}")
+    q_lo, q_hi = _band(q)
+    if not (0.0 <= q_lo <= q_hi <= 1.0):
+        raise ValueError(f"{fn}: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
+    return S, m, P, ncols, ldw, lds, ldk, q_lo, q_hi
+
+
+def _summary_outs(fn, out, m, ncols, dt, dev):
+    """The (mean, lo, hi) output checks the two share -> their common row stride ldo."""
+    if len(out) != 3:
+        raise ValueError(f"{fn}: out is (mean, lo, hi)")
+    ldo = max(ncols, 1)
+    for t in out:
+        if not torch.is_tensor(t) or t.dtype != dt or t.device != dev or \
+                tuple(t.shape) != (m, ncols):
+            raise ValueError(f"{fn}: out tensors must be {dt} of shape {(m, ncols)} on "
+                             "W3's device")
+        if ncols > 1 and t.stride(1) != 1:
+            raise ValueError(f"{fn}: out tensors need a unit column stride")
+        if m > 1:
+            ldo = max(ldo, t.stride(0))
+    for t in out:
+        if m > 1 and t.stride(0) != ldo:
+            raise ValueError(f"{fn}: out tensors must share one row stride >= ncols")
+    return ldo
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def field_summary(W3: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = None,
                   mu: torch.Tensor | None = None, err: torch.Tensor | None = None, q=0.025,
                   f32: bool = False, out=None):
@@ -185,66 +246,82 @@ def field_summary(W3: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = N
     sample-major) or None; ``q`` a float (band [q, 1 - q]) or a pair (q_lo, q_hi).  Each result is
     (m, ncols), float32 when ``f32`` else float64; ``out`` = three such tensors (unit column
     stride, one common row stride) to write into."""
-    for nm, t, nd in (("W3", W3, 3), ("K", K, 2)):
-        if not torch.is_tensor(t) or t.dtype != F64 or t.dim() != nd:
-            raise ValueError(f"field_summary: {nm} must be a {nd}-d float64 tensor")
-    S, m, P = W3.shape
+    fn = "field_summary"
+    S, m, P, ncols, ldw, lds, ldk, q_lo, q_hi = _summary_operands(fn, W3, K, sd, mu, err, q)
     dev = W3.device
-    if K.device != dev:
-        raise ValueError("field_summary: W3 and K must be on one device")
-    if S < 1 or P < 1 or K.shape[0] != P:
-        raise ValueError(f"field_summary: W3 {tuple(W3.shape)} needs S >= 1 samples and K "
-                         f"{tuple(K.shape)} one row per PC")
-    ncols = K.shape[1]
-    ldw = W3.stride(1) if m > 1 else max(W3.stride(1), P)
-    lds = W3.stride(0) if S > 1 else max(W3.stride(0), (m - 1) * ldw + P)
-    if (P > 1 and W3.stride(2) != 1) or ldw < P or lds < (max(m, 1) - 1) * ldw + P:
-        raise ValueError("field_summary: W3 needs a unit last stride and sample-major strides "
-                         f"(lds >= (m - 1) ldw + P, ldw >= P), got {W3.stride()}")
-    ldk = K.stride(0) if P > 1 else max(K.stride(0), ncols, 1)
-    if (ncols > 1 and K.stride(1) != 1) or ldk < max(ncols, 1):
-        raise ValueError(f"field_summary: K must be row-major (strides {K.stride()})")
-    if (sd is None) != (mu is None):
-        raise ValueError("field_summary: sd and mu go together")
-    for nm, t, n in (("sd", sd, ncols), ("mu", mu, ncols), ("err", err, S * m)):
-        if t is None:
-            continue
-        if t.dtype != F64 or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"field_summary: {nm} must be contiguous float64 on W3's device")
-        if t.numel() != n:
-            raise ValueError(f"field_summary: {nm} has {t.numel()} values, expected {n}")
-    q_lo, q_hi = _band(q)
-    if not (0.0 <= q_lo <= q_hi <= 1.0):
-        raise ValueError(f"field_summary: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
     dt = torch.float32 if f32 else F64
     if out is None:
         out = tuple(torch.empty((m, ncols), dtype=dt, device=dev) for _ in range(3))
-    if len(out) != 3:
-        raise ValueError("field_summary: out is (mean, lo, hi)")
-    ldo = max(ncols, 1)
-    for t in out:
-        if not torch.is_tensor(t) or t.dtype != dt or t.device != dev or \
-                tuple(t.shape) != (m, ncols):
-            raise ValueError(f"field_summary: out tensors must be {dt} of shape {(m, ncols)} on "
-                             "W3's device")
-        if ncols > 1 and t.stride(1) != 1:
-            raise ValueError("field_summary: out tensors need a unit column stride")
-        if m > 1:
-            ldo = max(ldo, t.stride(0))
-    for t in out:
-        if m > 1 and t.stride(0) != ldo:
-            raise ValueError("field_summary: out tensors must share one row stride >= ncols")
+    ldo = _summary_outs(fn, out, m, ncols, dt, dev)
     mean, lo, hi = out
     if dev.type != "cuda":
         raise ValueError("field_summary: the operands must be on a HIP device")
     if m == 0 or ncols == 0:
         return mean, lo, hi
     _capi.call("gp_field_summary", W3.data_ptr(), ldw, lds, S, m, P, K.data_ptr(), ldk, ncols,
-               sd.data_ptr() if sd is not None else None,
-               mu.data_ptr() if mu is not None else None,
-               err.data_ptr() if err is not None else None, q_lo, q_hi, mean.data_ptr(),
+               _ptr(sd), _ptr(mu), _ptr(err), q_lo, q_hi, mean.data_ptr(),
                lo.data_ptr(), hi.data_ptr(), ldo, int(f32), _stream(dev))
     return mean, lo, hi
+
+
+def field_score_ws_bytes(S: int, m: int, P: int, ncols: int) -> int:
+    return int(_capi.lib().gp_field_score_ws_bytes(S, m, P, ncols))
+
+
+def field_score(W3: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = None,
+                mu: torch.Tensor | None = None, err: torch.Tensor | None = None,
+                Y: torch.Tensor | None = None, q=0.025, mape_floor: float = -np.inf,
+                f32: bool = False, out=None, cols: bool = True):
+    """Test-error sums of field_summary's (mean, lo, hi) against the truth ``Y`` in the same one
+    pass, without the three arrays (gp_field_score): returns ``(rows, cols)``, fp64 device tensors
+    (m, 8) and (ncols, 4) in the order of _capi.SCORE_ROW / SCORE_COL (``cols=False``: None), and
+    ``(rows, cols, mean, lo, hi)`` when ``out`` = the three tensors field_summary would fill is
+    given (they receive the same bits).  W3, K, sd, mu, err, q, f32 as in field_summary; ``Y``
+    (m, ncols) float32 or float64 on the device with a unit column stride, NaN where there is no
+    truth, or None (no truth at all); absolute percentage errors are counted where
+    ``not (y < mape_floor)``."""
+    fn = "field_score"
+    S, m, P, ncols, ldw, lds, ldk, q_lo, q_hi = _summary_operands(fn, W3, K, sd, mu, err, q)
+    dev = W3.device
+    ldy = max(ncols, 1)
+    if Y is not None:
+        if not torch.is_tensor(Y) or Y.dtype not in (torch.float32, F64) or Y.device != dev or \
+                tuple(Y.shape) != (m, ncols):
+            raise ValueError(f"{fn}: Y must be float32 or float64 of shape {(m, ncols)} on W3's "
+                             "device")
+        if ncols > 1 and Y.stride(1) != 1:
+            raise ValueError(f"{fn}: Y needs a unit column stride")
+        if m > 1:
+            ldy = Y.stride(0)
+        if ldy < max(ncols, 1):
+            raise ValueError(f"{fn}: Y needs a row stride >= ncols (strides {Y.stride()})")
+    try:
+        mape_floor = float(mape_floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: mape_floor must be a number") from None
+    dt = torch.float32 if f32 else F64
+    ldo = max(ncols, 1)
+    if out is not None:
+        ldo = _summary_outs(fn, out, m, ncols, dt, dev)
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: the operands must be on a HIP device")
+    rows = torch.empty((m, 8), dtype=F64, device=dev)
+    colt = torch.empty((ncols, 4), dtype=F64, device=dev) if cols else None
+    res = (rows, colt) if out is None else (rows, colt) + tuple(out)
+    if m == 0 or ncols == 0:                       # sums of nothing
+        rows.zero_()
+        if colt is not None:
+            colt.zero_()
+        return res
+    nbytes = field_score_ws_bytes(S, m, P, ncols)
+    ws = _ws(nbytes, dev)
+    mean, lo, hi = out if out is not None else (None, None, None)
+    _capi.call("gp_field_score", W3.data_ptr(), ldw, lds, S, m, P, K.data_ptr(), ldk, ncols,
+               _ptr(sd), _ptr(mu), _ptr(err), q_lo, q_hi, _ptr(Y), ldy,
+               int(Y is not None and Y.dtype == torch.float32), mape_floor, _ptr(mean), _ptr(lo),
+               _ptr(hi), ldo, int(f32), rows.data_ptr(), _ptr(colt), ws.data_ptr(), nbytes,
+               _stream(dev))
+    return res
 
 
 def mean_var(x: torch.Tensor, ddof: int = 0):

@@ -28,6 +28,11 @@
 // same fma / add as its epilogue, so every sample value equals gp_field's bit for bit; the order
 // statistics are selections of those values (exact), the interpolation is numpy's _lerp with its
 // three roundings (no contraction), the mean is a fixed-order fp64 sum divided by S.
+//
+// gp_field_score is the same body with the reduction against a truth in the store's place
+// (summary_body<KS, KT, SCORE>, see there): row and column partial sums into a workspace, added in
+// a fixed order by score_reduce_kernel.  summary_kernel<KS, KT> is the SCORE = false instance and
+// compiles to the registers, LDS and scratch it had as a kernel of its own.
 #include "gpfit_common.h"
 #include "../../include/gpfit.h"
 
@@ -88,21 +93,77 @@ GP_DEV double sum_lerp(double a, double b, double t) {
   return t >= 0.5 ? dn : up;
 }
 
+// gp_field_score's operands beside the summary's: the truth, the MAPE floor, the partials
+struct ScoreK {
+  const void* Y;
+  long long ldy;
+  int y_f32;
+  double floor;
+  double* rowp;   // 8 doubles per unit (GPFIT_SCORE_ROW_* order)
+  double* colp;   // per segment 4 x kSumCols doubles (GPFIT_SCORE_COL_* order); may be null
+};
+
+// the lower lane's terms of one element: (mu - y)^2 and |(mu - y) / y|, every operation rounded
+// on its own (numpy's terms bit for bit)
+GP_DEV void score_resid(double mv, double y, double* sq, double* ape) {
+#pragma clang fp contract(off)
+  const double r = mv - y;
+  *sq = r * r;
+  *ape = fabs(r / y);
+}
+
 // KS = k-steps of 4 (P <= 4 KS), KT = list depth per tail.  Work units are (column panel, test
 // point) pairs, panel-major; block i takes units [i U / B, (i + 1) U / B) of the U = npanels x m.
-template <int KS, int KT>
-__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kernel(
+//
+// SCORE (gp_field_score): the same chain, fold and merge, and instead of (or beside) the three
+// stores the unit's terms against the truth Y.  After the merge the lane pair of a column (lanes
+// 32 apart: lower tail, upper tail) trades l and h as stored; the lower lane forms the residual
+// terms, the upper one the band terms.  Row sums: an xor-shuffle reduction over each 32-lane half,
+// the four waves' results through LDS (two slots, alternating per unit, read after the tile loop's
+// own barrier), one partial of 8 doubles per unit at rowp + 8 u.  Column sums: one double and one
+// count per lane, kept while the block stays on a panel and stored per (block, panel) segment
+// blockIdx + panel at colp.  Every partial has one writer and a fixed order: no atomics.
+template <int KS, int KT, bool SCORE>
+GP_DEV void summary_body(
     const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
     const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
     const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
     void* __restrict__ mean, void* __restrict__ lo, void* __restrict__ hi, long long ldo,
-    int out_f32, int nts) {
+    int out_f32, int nts, const ScoreK& sc) {
   constexpr int KP = 4 * KS;                               // padded inner dimension
   constexpr int kSumRows = sum_rows<KS>(), RS = kSumRows / 16;
   constexpr int NLD = (kSumRows * KP + kSumThreads - 1) / kSumThreads;   // per thread
   __shared__ double ws[2][kSumRows * kSumPitch];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int li = lane & 15, lk = lane >> 4;
+  // SCORE: the lane's column accumulator (lower lane: sum of squared residuals and valid count,
+  // upper lane: sum of widths and covered count), the row slot in use
+  [[maybe_unused]] double col_s = 0.0;
+  [[maybe_unused]] int col_n = 0, rp = 0;
+  [[maybe_unused]] double* rsh = nullptr;
+  if constexpr (SCORE) {
+    __shared__ double row_sh[2][kSumWaves][8];
+    rsh = &row_sh[0][0][0];
+  }
+  // the finished unit's row partial: the four waves' sums in wave order
+  [[maybe_unused]] auto flush_row = [&](long long unit) {
+    if (threadIdx.x < 8) {
+      const double* r = rsh + rp * (kSumWaves * 8) + threadIdx.x;
+      sc.rowp[unit * 8 + threadIdx.x] = ((r[0] + r[8]) + r[16]) + r[24];
+    }
+    rp ^= 1;
+  };
+  [[maybe_unused]] auto flush_cols = [&](long long pan) {
+    if (sc.colp) {
+      const int idx = wv * kSumWaveCols + 16 * (lk & 1) + li;
+      double* seg = sc.colp + ((long long)blockIdx.x + pan) * (4 * kSumCols) + idx;
+      const bool upl = lk >> 1;
+      seg[(upl ? 3 : 0) * kSumCols] = col_s;
+      seg[(upl ? 2 : 1) * kSumCols] = (double)col_n;
+    }
+    col_s = 0.0;
+    col_n = 0;
+  };
   const long long npanels = (ncols + kSumCols - 1) / kSumCols;
   const long long units = npanels * m;
   const long long u0 = units * blockIdx.x / gridDim.x;
@@ -227,6 +288,15 @@ __global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kern
       // the unit is complete.  Exchange 1 (lanes 16 apart): the even lk keeps column tile 0 and
       // takes its partner's tile-0 state, the odd one tile 1.
       const bool odd = lk & 1, up = lk >> 1;
+      [[maybe_unused]] double yv = __builtin_nan("");      // stays NaN: no truth for this element
+      if constexpr (SCORE) {
+        const int c = (int)panel * kSumCols + wv * kSumWaveCols + 16 * (int)odd + li;
+        if (sc.Y && c < ncols) {                           // in flight under the merge
+          const long long o = (long long)i * sc.ldy + c;
+          yv = sc.y_f32 ? (double)static_cast<const float*>(sc.Y)[o]
+                        : static_cast<const double*>(sc.Y)[o];
+        }
+      }
       double L[KT], N[KT], R[KT];
 #pragma unroll
       for (int j = 0; j < KT; ++j) {
@@ -268,23 +338,95 @@ __global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kern
       }
       const double qv = sum_lerp(va, vb, t);
       const int c = (int)panel * kSumCols + wv * kSumWaveCols + 16 * (int)odd + li;
-      if (c < ncols) {
-        const long long o = (long long)i * ldo + c;
-        void* qp = up ? hi : lo;
-        if (out_f32) {
-          static_cast<float*>(qp)[o] = static_cast<float>(qv);
-          if (!up) static_cast<float*>(mean)[o] = static_cast<float>(sm / (double)S);
+      if constexpr (!SCORE) {
+        if (c < ncols) {
+          const long long o = (long long)i * ldo + c;
+          void* qp = up ? hi : lo;
+          if (out_f32) {
+            static_cast<float*>(qp)[o] = static_cast<float>(qv);
+            if (!up) static_cast<float*>(mean)[o] = static_cast<float>(sm / (double)S);
+          } else {
+            static_cast<double*>(qp)[o] = qv;
+            if (!up) static_cast<double*>(mean)[o] = sm / (double)S;
+          }
+        }
+      } else {
+        const bool in_c = c < ncols;
+        const double mv = sm / (double)S;
+        // the values as stored (each output is optional), widened again
+        const double qs = out_f32 ? (double)static_cast<float>(qv) : qv;
+        const double ms = out_f32 ? (double)static_cast<float>(mv) : mv;
+        if (in_c) {
+          const long long o = (long long)i * ldo + c;
+          void* qp = up ? hi : lo;
+          if (out_f32) {
+            if (qp) static_cast<float*>(qp)[o] = static_cast<float>(qv);
+            if (!up && mean) static_cast<float*>(mean)[o] = static_cast<float>(mv);
+          } else {
+            if (qp) static_cast<double*>(qp)[o] = qv;
+            if (!up && mean) static_cast<double*>(mean)[o] = mv;
+          }
+        }
+        const double qo = __shfl_xor(qs, 32);              // the pair's other quantile
+        const double lv = up ? qo : qs, hv = up ? qs : qo;
+        const bool valid = yv == yv;                       // implies in_c and Y given
+        double ta, tb, tc = 0.0;                           // this lane's three row terms
+        int tn;                                            // and its counts, 8 bits each
+        if (up) {
+          const bool cov = valid && lv <= yv && yv <= hv;
+          ta = in_c ? lv : 0.0;
+          tb = in_c ? hv : 0.0;
+          tn = cov;
+          col_s += in_c ? hv - lv : 0.0;
+          col_n += cov;
         } else {
-          static_cast<double*>(qp)[o] = qv;
-          if (!up) static_cast<double*>(mean)[o] = sm / (double)S;
+          double sq = 0.0, ape = 0.0;
+          if (valid) score_resid(ms, yv, &sq, &ape);
+          const bool cnt = valid && !(yv < sc.floor);
+          ta = sq;
+          tb = cnt ? ape : 0.0;
+          tc = in_c ? ms : 0.0;
+          tn = (int)valid | ((int)cnt << 8);
+          col_s += sq;
+          col_n += valid;
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {                // within the 32-lane half
+          ta += __shfl_xor(ta, d);
+          tb += __shfl_xor(tb, d);
+          tc += __shfl_xor(tc, d);
+          tn += __shfl_xor(tn, d);
+        }
+        double* r = rsh + (rp * kSumWaves + wv) * 8;
+        if (lane == 0) {
+          r[0] = ta;
+          r[1] = (double)(tn & 255);
+          r[2] = tb;
+          r[3] = (double)(tn >> 8);
+          r[7] = tc;
+        } else if (lane == 32) {
+          r[4] = ta;
+          r[5] = tb;
+          r[6] = (double)tn;
         }
       }
     }
-    if (!more) break;
+    if (!more) {
+      if constexpr (SCORE) {
+        __syncthreads();
+        flush_row(u);
+        flush_cols(panel);
+      }
+      break;
+    }
     store_tile(buf ^ 1);                                   // the other buffer: last read a tile ago
     __syncthreads();
     buf ^= 1;
     if (tsn == 0) {
+      if constexpr (SCORE) {
+        flush_row(u);
+        if (in == 0) flush_cols(panel);
+      }
       if (in == 0) ++panel;
       reset(panel);
     }
@@ -292,6 +434,74 @@ __global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kern
     i = in;
     u = un;
   }
+}
+
+template <int KS, int KT>
+__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kernel(
+    const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
+    const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
+    const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
+    void* __restrict__ mean, void* __restrict__ lo, void* __restrict__ hi, long long ldo,
+    int out_f32, int nts) {
+  summary_body<KS, KT, false>(W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, err, tlo, thi, mean,
+                              lo, hi, ldo, out_f32, nts, ScoreK{});
+}
+
+template <int KS, int KT>
+__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void score_kernel(
+    const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
+    const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
+    const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
+    void* __restrict__ mean, void* __restrict__ lo, void* __restrict__ hi, long long ldo,
+    int out_f32, int nts, ScoreK sc) {
+  summary_body<KS, KT, true>(W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, err, tlo, thi, mean,
+                             lo, hi, ldo, out_f32, nts, sc);
+}
+
+// first block of a `grid`-block launch whose unit range [units b / grid, units (b + 1) / grid)
+// holds unit u
+GP_DEV long long score_block_of(long long u, long long units, long long grid) {
+  long long b = u * grid / units;
+  while (b + 1 < grid && units * (b + 1) / grid <= u) ++b;
+  while (b > 0 && units * b / grid > u) --b;
+  return b;
+}
+
+// The partials of score_kernel -> rows and cols, every sum in a fixed order.  Block i < m: row i,
+// thread t adds the partials of panels t / 8 + 32 j for value t % 8, then thread k < 8 the 32
+// strands in order.  The blocks after those: one thread per column, the segments of the blocks
+// (of the `grid` that ran) whose unit range meets the column's panel, in block order.
+__global__ __launch_bounds__(256) void score_reduce_kernel(
+    const double* __restrict__ rowp, const double* __restrict__ colp, int m, int ncols,
+    long long npanels, long long grid, double* __restrict__ rows, double* __restrict__ cols) {
+  __shared__ double sh[256];
+  if ((int)blockIdx.x < m) {
+    const int i = blockIdx.x, k = threadIdx.x & 7;
+    double s = 0.0;
+    for (long long p = threadIdx.x >> 3; p < npanels; p += 32) s += rowp[(p * m + i) * 8 + k];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x < 8) {
+      double t = 0.0;
+      for (int g = 0; g < 32; ++g) t += sh[8 * g + threadIdx.x];
+      rows[(long long)i * 8 + threadIdx.x] = t;
+    }
+    return;
+  }
+  const long long c = (long long)(blockIdx.x - m) * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  const long long p = c / kSumCols, units = npanels * m;
+  const int idx = (int)(c % kSumCols);
+  const long long b0 = score_block_of(p * m, units, grid);
+  const long long b1 = score_block_of(p * m + m - 1, units, grid);
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (long long b = b0; b <= b1; ++b) {
+    const double* seg = colp + (b + p) * (4 * kSumCols) + idx;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] += seg[j * kSumCols];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cols[c * 4 + j] = a[j];
 }
 
 struct SumArgs {
@@ -307,6 +517,8 @@ struct SumArgs {
   long long ldo;
   int out_f32;
   hipStream_t stream;
+  ScoreK sc;      // gp_field_score only
+  double *rows, *cols;
 };
 
 // blocks of an instantiation that fit a CU at once (registers and LDS, from the runtime)
@@ -335,14 +547,56 @@ hipError_t launch_summary(const SumArgs& a) {
   return hipGetLastError();
 }
 
-template <int KT>
+template <int KS, int KT>
+int score_blocks_per_cu() {
+  static const int nb = [] {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, score_kernel<KS, KT>, kSumThreads,
+                                                     0) != hipSuccess || n < 1)
+      n = sum_occ<KS, KT>();
+    return n;
+  }();
+  return nb;
+}
+
+// blocks of the score launch: one residency round as the summary's, and never more than the
+// workspace has segments for
+constexpr long long kScoreMaxBlocks = 2048;
+
+template <int KS, int KT>
+hipError_t launch_score(const SumArgs& a) {
+  const long long npanels = gp_ceil_div(a.ncols, kSumCols), units = npanels * a.m;
+  const int nts = (a.S + sum_rows<KS>() - 1) / sum_rows<KS>();
+  long long blocks = (long long)gp_num_cus() * score_blocks_per_cu<KS, KT>();
+  if (blocks > kScoreMaxBlocks) blocks = kScoreMaxBlocks;
+  if (blocks > units) blocks = units;
+  hipLaunchKernelGGL((score_kernel<KS, KT>), dim3((unsigned)blocks), dim3(kSumThreads), 0,
+                     a.stream, a.W, a.ldw, a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu,
+                     a.err, a.tlo, a.thi, a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts, a.sc);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const unsigned rblocks = (unsigned)a.m + (a.cols ? (unsigned)gp_ceil_div(a.ncols, 256) : 0u);
+  hipLaunchKernelGGL(score_reduce_kernel, dim3(rblocks), dim3(256), 0, a.stream, a.sc.rowp,
+                     a.sc.colp, a.m, a.ncols, npanels, blocks, a.rows, a.cols);
+  return hipGetLastError();
+}
+
+template <int KT, bool SCORE>
 hipError_t dispatch_summary_ks(const SumArgs& a) {
   const int ks = (a.P + 3) / 4;
-  if (ks <= 2) return launch_summary<2, KT>(a);
-  if (ks <= 4) return launch_summary<4, KT>(a);
-  if (ks <= 8) return launch_summary<8, KT>(a);
-  if (ks <= 12) return launch_summary<12, KT>(a);
-  return launch_summary<16, KT>(a);
+  if constexpr (SCORE) {
+    if (ks <= 2) return launch_score<2, KT>(a);
+    if (ks <= 4) return launch_score<4, KT>(a);
+    if (ks <= 8) return launch_score<8, KT>(a);
+    if (ks <= 12) return launch_score<12, KT>(a);
+    return launch_score<16, KT>(a);
+  } else {
+    if (ks <= 2) return launch_summary<2, KT>(a);
+    if (ks <= 4) return launch_summary<4, KT>(a);
+    if (ks <= 8) return launch_summary<8, KT>(a);
+    if (ks <= 12) return launch_summary<12, KT>(a);
+    return launch_summary<16, KT>(a);
+  }
 }
 
 // numpy's "linear" rule: pos = q (S - 1), j = floor(pos), t = pos - j
@@ -353,15 +607,11 @@ void summary_position(double q, int S, int* j, double* t) {
   *t = pos - f;
 }
 
-}  // namespace
-
-extern "C" int gp_field_summary_max_tail(void) { return kSumMaxTail; }
-
-extern "C" int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m, int P,
-                                const double* K, long long ldk, int ncols, const double* sd,
-                                const double* mu, const double* err, double q_lo, double q_hi,
-                                void* mean, void* lo, void* hi, long long ldo, int out_f32,
-                                hipStream_t stream) {
+// the checks gp_field_summary and gp_field_score share (arguments 1-14, the same numbers in
+// both), and the two tails of a valid request
+int summary_check(const double* W, long long ldw, long long lds, int S, int m, int P,
+                  const double* K, long long ldk, int ncols, const double* sd, const double* mu,
+                  double q_lo, double q_hi, SumTail* a_lo, SumTail* a_hi, int* depth) {
   if (!W) return -1;
   if (ldw < P || ldw < 1) return -2;
   if (lds < 1 || lds < (m > 0 ? m - 1 : 0) * ldw + P) return -3;
@@ -383,20 +633,88 @@ extern "C" int gp_field_summary(const double* W, long long ldw, long long lds, i
   const int dlo = jl + 2 < S ? jl + 2 : S, dhi = S - jh;
   if (dlo > kSumMaxTail) return -13;
   if (dhi > kSumMaxTail) return -14;
+  const int jl1 = jl + 1 < S ? jl + 1 : jl, jh1 = jh + 1 < S ? jh + 1 : jh;
+  // the upper list holds -z ascending: z_(j) is its entry S - 1 - j
+  *a_lo = {jl, jl1, jl1 == jl ? 0.0 : tl};
+  *a_hi = {S - 1 - jh, S - 1 - jh1, jh1 == jh ? 0.0 : th};
+  *depth = dlo > dhi ? dlo : dhi;
+  return 0;
+}
+
+template <bool SCORE>
+hipError_t dispatch_summary(const SumArgs& a, int depth) {
+  return depth <= 2   ? dispatch_summary_ks<2, SCORE>(a)
+         : depth <= 4 ? dispatch_summary_ks<4, SCORE>(a)
+                      : dispatch_summary_ks<8, SCORE>(a);
+}
+
+// workspace of gp_field_score: the row partials (8 doubles per unit), then the column segments
+long long score_ws_layout(long long m, long long ncols, long long* col_off) {
+  const long long npanels = (ncols + kSumCols - 1) / kSumCols, units = npanels * m;
+  const long long nb = units < kScoreMaxBlocks ? units : kScoreMaxBlocks;
+  const long long rows_b = align256(units * 8 * (long long)sizeof(double));
+  if (col_off) *col_off = rows_b;
+  return rows_b + align256((npanels + nb - 1) * 4 * kSumCols * (long long)sizeof(double));
+}
+
+}  // namespace
+
+extern "C" int gp_field_summary_max_tail(void) { return kSumMaxTail; }
+
+extern "C" int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m, int P,
+                                const double* K, long long ldk, int ncols, const double* sd,
+                                const double* mu, const double* err, double q_lo, double q_hi,
+                                void* mean, void* lo, void* hi, long long ldo, int out_f32,
+                                hipStream_t stream) {
+  SumTail a_lo, a_hi;
+  int depth;
+  const int rc = summary_check(W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, q_lo, q_hi, &a_lo,
+                               &a_hi, &depth);
+  if (rc) return rc;
   if (!mean) return -15;
   if (!lo) return -16;
   if (!hi) return -17;
   if (ldo < ncols || ldo < 1) return -18;
   if (m == 0 || ncols == 0) return 0;
-  const int jl1 = jl + 1 < S ? jl + 1 : jl, jh1 = jh + 1 < S ? jh + 1 : jh;
-  // the upper list holds -z ascending: z_(j) is its entry S - 1 - j
-  const SumTail a_lo = {jl, jl1, jl1 == jl ? 0.0 : tl};
-  const SumTail a_hi = {S - 1 - jh, S - 1 - jh1, jh1 == jh ? 0.0 : th};
   const SumArgs a = {W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, err, a_lo, a_hi,
-                     mean, lo, hi, ldo, out_f32, stream};
-  const int depth = dlo > dhi ? dlo : dhi;
-  const hipError_t e = depth <= 2   ? dispatch_summary_ks<2>(a)
-                       : depth <= 4 ? dispatch_summary_ks<4>(a)
-                                    : dispatch_summary_ks<8>(a);
+                     mean, lo, hi, ldo, out_f32, stream, ScoreK{}, nullptr, nullptr};
+  const hipError_t e = dispatch_summary<false>(a, depth);
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}
+
+extern "C" long long gp_field_score_ws_bytes(int S, int m, int P, int ncols) {
+  if (S < 1 || m < 0 || P < 1 || ncols < 0) return -1;
+  if (m == 0 || ncols == 0) return 0;
+  return score_ws_layout(m, ncols, nullptr);
+}
+
+extern "C" int gp_field_score(const double* W, long long ldw, long long lds, int S, int m, int P,
+                              const double* K, long long ldk, int ncols, const double* sd,
+                              const double* mu, const double* err, double q_lo, double q_hi,
+                              const void* Y, long long ldy, int y_f32, double mape_floor,
+                              void* mean, void* lo, void* hi, long long ldo, int out_f32,
+                              double* rows, double* cols, void* ws, long long ws_bytes,
+                              hipStream_t stream) {
+  SumTail a_lo, a_hi;
+  int depth;
+  const int rc = summary_check(W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, q_lo, q_hi, &a_lo,
+                               &a_hi, &depth);
+  if (rc) return rc;
+  if (Y && (ldy < ncols || ldy < 1)) return -16;
+  if (y_f32 != 0 && y_f32 != 1) return -17;
+  if ((mean || lo || hi) && (ldo < ncols || ldo < 1)) return -22;
+  if (out_f32 != 0 && out_f32 != 1) return -23;
+  if (!rows) return -24;
+  if (m == 0 || ncols == 0) return 0;
+  long long col_off;
+  const long long need = score_ws_layout(m, ncols, &col_off);
+  if (!ws || ((size_t)ws & 255)) return -26;
+  if (ws_bytes < need) return -27;
+  const ScoreK sc = {Y, ldy, y_f32, mape_floor, static_cast<double*>(ws),
+                     cols ? reinterpret_cast<double*>(static_cast<char*>(ws) + col_off)
+                          : nullptr};
+  const SumArgs a = {W, ldw, lds, S, m, P, K, ldk, ncols, sd, mu, err, a_lo, a_hi,
+                     mean, lo, hi, ldo, out_f32, stream, sc, rows, cols};
+  const hipError_t e = dispatch_summary<true>(a, depth);
   return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
 }

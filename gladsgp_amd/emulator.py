@@ -574,13 +574,32 @@ class EmulatorPrediction:
             return None
         sd_ = self.model.data.sim_data
         dev = self.model.device
-        S, m, P = self.S, self.m, self.P
-        ny = sd_.K.shape[1]
+        m, ny = self.m, sd_.K.shape[1]
+        wd, sd, mu, e, q_lo, q_hi, f32 = self._summary_inputs("summary", q, std, add_error, rng,
+                                                              per_point, w)
+        dt = torch.float32 if f32 else F64
+        if out is None:
+            out = tuple(torch.empty((m, ny), dtype=dt, device=dev) for _ in range(3))
+        if self._summary_fused(q_lo, q_hi):
+            blas.field_summary(wd, sd_.K, sd, mu, e, q=(q_lo, q_hi), f32=f32, out=out)
+        else:
+            self._summary_blocks(wd, sd, mu, e, q_lo, q_hi, out)
+        if not to_host:
+            return out
+        return tuple(_to_host(t, np.float32 if f32 else np.float64) for t in out)
+
+    def _summary_inputs(self, fn, q, std, add_error, rng, per_point, w):
+        """The operands summary() and score() hand to the kernel: (w (S, m, P) fp64 on the
+        device, sd, mu, the S m error scalars or None, q_lo, q_hi, float32 outputs?).  One
+        error_draws call: the same ``rng`` gives the same draws in both and in get_y()."""
+        sd_ = self.model.data.sim_data
+        dev = self.model.device
+        S, m = self.S, self.m
         f32 = w is None and self._w_dtype == np.float32
         wd = (self.w_dev if w is None else _to_device_f64(w, dev)).contiguous()
         q_lo, q_hi = blas._band(q)
         if not (0.0 <= q_lo <= q_hi <= 1.0):
-            raise ValueError(f"summary: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
+            raise ValueError(f"{fn}: need 0 <= q_lo <= q_hi <= 1, got ({q_lo}, {q_hi})")
         e = None
         if add_error:
             e = torch.as_tensor(self.error_draws(rng, per_point), dtype=F64, device=dev)
@@ -588,17 +607,95 @@ class EmulatorPrediction:
         mu = sd = None
         if not std:
             mu, sd = sd_.y_mean.contiguous(), sd_.y_sd.contiguous()
+        return wd, sd, mu, e, q_lo, q_hi, f32
+
+    def _summary_fused(self, q_lo, q_hi) -> bool:
+        """Whether gp_field_summary / gp_field_score take this prediction (PCs and tail depth)."""
+        return self.P <= blas.field_max_pcs() and \
+            max(blas.summary_tail_depths(self.S, q_lo, q_hi)) <= blas.field_summary_max_tail()
+
+    def score(self, y_true, q=0.025, mape_floor=None, std: bool = False, add_error: bool = True,
+              rng=None, per_point: bool = True, w=None, maps: bool = False,
+              to_host: bool = True, cols: bool = True):
+        """Test-error scores of summary(q, ...) against ``y_true`` (m, ny) -- RMSE, MAPE, mean
+        quantiles, coverage per test point and RMSE, coverage, band width per node, the block
+        assess_all_models.py:524-552 and plot_integrated_RMSE.py:108-116 compute from three
+        (m, ny) arrays -- as a :class:`gladsgp_amd.score.FieldScore`, in summary()'s one pass and
+        without the arrays: the kernel (gp_field_score) writes m x 8 and ny x 4 sums.
+
+        ``y_true``: numpy or a device tensor, float32 or float64 (a host array is uploaded in its
+        own dtype), NaN where there is no truth; None scores the prediction alone (mean
+        quantiles and widths: the integration-point loop of assess_all_models.py:504-521).
+        ``mape_floor``: absolute percentage errors count where ``not (y < mape_floor)`` (the
+        reference's ``inner_mape[y_test < lq] = nan``); None counts every valid element.  q, std,
+        add_error, rng, per_point, w and the float32 rule are summary()'s: the same ``rng`` gives
+        the same error draws.  ``maps=True`` also returns summary()'s three arrays (``.maps``),
+        the same bits, from the same pass.  Cross-validated predictions leave the simulations in no
+        fold (NaN weights) out of the pass: their rows are NaN with zero counts, they enter no
+        per-node sum, and the per-node means are over the ``n_scored`` other points.  ``to_host=False`` keeps the raw sums and maps on the device.
+        Beyond the kernel's limits (PCs, tail depth) the maps are built as summary() builds them
+        and reduced with torch: the same results to rounding.  Distributed predictions: computed
+        on rank 0, None on the other ranks."""
+        from . import score as gscore
+        ctx = self.ctx
+        if ctx is not None and ctx.distributed and ctx.rank != 0:
+            return None
+        sd_ = self.model.data.sim_data
+        dev = self.model.device
+        S, m, P = self.S, self.m, self.P
+        ny = sd_.K.shape[1]
+        wd, sd, mu, e, q_lo, q_hi, f32 = self._summary_inputs("score", q, std, add_error, rng,
+                                                              per_point, w)
+        Y = None
+        if y_true is not None:
+            Y = y_true if torch.is_tensor(y_true) else torch.as_tensor(np.asarray(y_true))
+            if Y.dtype not in (torch.float32, F64):
+                Y = Y.to(F64)
+            if tuple(Y.shape) != (m, ny):
+                raise ValueError(f"score: y_true must be {(m, ny)}, got {tuple(Y.shape)}")
+            Y = Y.to(dev)
+            if ny > 1 and Y.stride(1) != 1:
+                Y = Y.contiguous()
+        floor = -np.inf if mape_floor is None else float(mape_floor)
+        keep = self._points_with_prediction(wd)
+        part = keep is not None and not bool(keep.all())
+        if part:
+            wd = wd[:, keep].contiguous()
+            e = None if e is None else e.reshape(S, m)[:, keep].reshape(-1).contiguous()
+            Y = None if Y is None else Y[keep]
+        mk = wd.shape[1]
         dt = torch.float32 if f32 else F64
-        if out is None:
-            out = tuple(torch.empty((m, ny), dtype=dt, device=dev) for _ in range(3))
-        if P <= blas.field_max_pcs() and \
-                max(blas.summary_tail_depths(S, q_lo, q_hi)) <= blas.field_summary_max_tail():
-            blas.field_summary(wd, sd_.K, sd, mu, e, q=(q_lo, q_hi), f32=f32, out=out)
+        fused = self._summary_fused(q_lo, q_hi)
+        out = None
+        if maps or not fused:
+            out = tuple(torch.empty((mk, ny), dtype=dt, device=dev) for _ in range(3))
+        if fused:
+            res = blas.field_score(wd, sd_.K, sd, mu, e, Y, q=(q_lo, q_hi), mape_floor=floor,
+                                   f32=f32, out=out, cols=cols)
+            rows, colt = res[0], res[1]
         else:
             self._summary_blocks(wd, sd, mu, e, q_lo, q_hi, out)
-        if not to_host:
-            return out
-        return tuple(_to_host(t, np.float32 if f32 else np.float64) for t in out)
+            rows, colt = gscore.sums_from_maps(*out, Y, floor, cols=cols)
+        if part:
+            rows = gscore.rows_without_prediction(rows, keep, m)
+            if maps:
+                full = tuple(torch.full((m, ny), float("nan"), dtype=dt, device=dev)
+                             for _ in range(3))
+                for f, o in zip(full, out):
+                    f[keep] = o
+                out = full
+        if to_host:
+            rows = rows.cpu().numpy()
+            colt = None if colt is None else colt.cpu().numpy()
+            if maps:
+                out = tuple(_to_host(t, np.float32 if f32 else np.float64) for t in out)
+        return gscore.FieldScore(rows, colt, ny, out if maps else None, n_scored=mk)
+
+    def _points_with_prediction(self, wd):
+        """score(): a bool (m,) mask of the test points to score, or None for all of them.  Every
+        point of an ordinary prediction has weights, so nothing is looked at here;
+        EmulatorXvalPrediction leaves out the simulations in no fold."""
+        return None
 
     def _summary_blocks(self, wd, sd, mu, e, q_lo, q_hi, out) -> None:
         """summary()'s generic route: the fp64 field of a block of test points (at most 1 GiB),
@@ -725,6 +822,22 @@ class EmulatorXvalPrediction(EmulatorPrediction):
                          out=(mean[a:b], var[a:b]))
         self.shift_dev = shift_u.reshape(S, 1, P)
         self._set_results(None, realize, seed, (mean, var))
+
+    def score(self, y_true=None, q=0.025, mape_floor=None, std: bool = False, **kw):
+        """EmulatorPrediction.score() of the cross-validated field against the training
+        simulations themselves (``y_true`` None: sim_data.y, or the standardised y_std with
+        ``std``): include_trunc_error.py's and assess_all_models.py:32's use of the
+        cross-validated predictions.  Simulations in no fold have NaN rows and zero counts and
+        are left out of the per-node statistics.  Because None selects the training simulations
+        here, the prediction-only score of the base class (no truth at all) is not reachable
+        through this method: call ``EmulatorPrediction.score(xval, None, ...)`` for it."""
+        if y_true is None:
+            sd_ = self.model.data.sim_data
+            y_true = sd_.y_std if std else sd_.y_dev       # sim_data.y, already on the device
+        return super().score(y_true, q=q, mape_floor=mape_floor, std=std, **kw)
+
+    def _points_with_prediction(self, wd):
+        return ~torch.isnan(wd).any(dim=2).any(dim=0)
 
     @property
     def standardized_residuals(self) -> np.ndarray:

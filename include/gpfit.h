@@ -473,6 +473,56 @@ int gp_field_summary(const double* W, long long ldw, long long lds, int S, int m
                      const double* mu, const double* err, double q_lo, double q_hi, void* mean,
                      void* lo, void* hi, long long ldo, int out_f32, hipStream_t stream);
 
+/* Test-error scores of the reconstructed field against a truth, the numbers the assessment drivers
+ * reduce the summary to (assess_all_models.py:524-552: RMSE, MAPE, mean quantiles, coverage;
+ * plot_integrated_RMSE.py:108-116: per-node RMSE; assess_all_models.py:504-521, 538: the band
+ * width where there is no truth), in gp_field_summary's one pass and without its three (m, ncols)
+ * arrays.  Arguments 1-14 are gp_field_summary's, with the same limits and the same codes.  Let
+ * mu, l, h be what gp_field_summary stores at (i, c) as mean, lo, hi -- with out_f32 = 1 the
+ * float32 values, widened again -- and y = Y[i*ldy + c] (float32 when y_f32 = 1, else fp64,
+ * widened exactly; ldy >= ncols).  An element is valid when Y is given and y is not NaN (the
+ * reference's nanmean).  Every term is formed in fp64 with each operation rounded on its own
+ * ((mu - y)^2 is a rounded difference, squared and rounded: numpy's terms bit for bit), then
+ *   rows[i*8 + k], summed over c < ncols:                       cols[c*4 + k], summed over i < m:
+ *     GPFIT_SCORE_ROW_SQERR   sum (mu - y)^2 over valid           GPFIT_SCORE_COL_SQERR  the same
+ *     GPFIT_SCORE_ROW_VALID   number of valid elements            GPFIT_SCORE_COL_VALID  the same
+ *     GPFIT_SCORE_ROW_APE     sum |(mu - y) / y| over valid       GPFIT_SCORE_COL_COVERED
+ *                             elements with !(y < mape_floor)     GPFIT_SCORE_COL_WIDTH  sum (h - l)
+ *     GPFIT_SCORE_ROW_APE_N   the number of those elements
+ *     GPFIT_SCORE_ROW_LO / _HI / _MEAN   sum of l / h / mu over all c
+ *     GPFIT_SCORE_ROW_COVERED number of valid elements with l <= y <= h (both inclusive)
+ * counts as doubles (exact).  mape_floor is the reference's inner_mape[y_test < lq] = nan: -inf
+ * counts every valid element, +inf none but y = +inf; a NaN floor compares false like numpy's
+ * mask and so counts every valid element too.  Y NULL: no element is valid (the widths and the
+ * sums of l, h, mu remain: the integration-point loop).  mean, lo, hi are optional outputs, each
+ * NULL or m x ncols with row stride ldo >= ncols in the out_f32 dtype: what gp_field_summary
+ * stores there, bit for bit.  cols may be NULL.  ws: gp_field_score_ws_bytes(S, m, P, ncols)
+ * bytes, 256-B aligned (8 doubles per (128-column panel, point) and 4 x 128 per (workgroup, panel)
+ * segment; -1 for an invalid size, 0 for an empty problem).  A second small kernel on the same
+ * stream adds the partials in a fixed order: no floating-point atomics, no hand-off between
+ * workgroups, equal inputs give equal bits.  The new arguments are checked after the shared ones,
+ * each by its own number: -16 ldy, -17 y_f32, -22 ldo (when an output is given), -23 out_f32,
+ * -24 rows, -26 ws (NULL or misaligned), -27 ws_bytes.  m = 0 or ncols = 0: no launch, ws unused. */
+#define GPFIT_SCORE_ROW_SQERR 0
+#define GPFIT_SCORE_ROW_VALID 1
+#define GPFIT_SCORE_ROW_APE 2
+#define GPFIT_SCORE_ROW_APE_N 3
+#define GPFIT_SCORE_ROW_LO 4
+#define GPFIT_SCORE_ROW_HI 5
+#define GPFIT_SCORE_ROW_COVERED 6
+#define GPFIT_SCORE_ROW_MEAN 7
+#define GPFIT_SCORE_COL_SQERR 0
+#define GPFIT_SCORE_COL_VALID 1
+#define GPFIT_SCORE_COL_COVERED 2
+#define GPFIT_SCORE_COL_WIDTH 3
+long long gp_field_score_ws_bytes(int S, int m, int P, int ncols);
+int gp_field_score(const double* W, long long ldw, long long lds, int S, int m, int P,
+                   const double* K, long long ldk, int ncols, const double* sd, const double* mu,
+                   const double* err, double q_lo, double q_hi, const void* Y, long long ldy,
+                   int y_f32, double mape_floor, void* mean, void* lo, void* hi, long long ldo,
+                   int out_f32, double* rows, double* cols, void* ws, long long ws_bytes,
+                   hipStream_t stream);
+
 /* Saltelli estimators of the Sobol' sensitivity indices for R replicates of the design rows: the
  * statistic that saltelli_sensitivity_indices / PCA_saltelli_sensitivity_indices evaluate once
  * for the point estimate and then 9,999 times per scipy.stats.bootstrap call, plus N jackknife
