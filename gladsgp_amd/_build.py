@@ -18,14 +18,17 @@ LIB_PATH = os.path.join(PKG_DIR, "libgpfit.so")
 TRACE_LIB_PATH = os.path.join(PKG_DIR, "libgpfit_trace.so")
 SOURCES = ["gram.hip", "chol.hip", "predict.hip", "linalg.hip", "profile.hip", "blas.hip",
            "eig.hip", "comm.hip", "rng.hip", "mcmc.hip", "host_rng.hip", "field.hip",
-           "summary.hip", "sobol.hip", "xval.hip"]
+           "summary.hip", "sobol.hip", "xval.hip", "pcatrunc.hip"]
 # Per-file extra flags.  chol.hip: MFMA accumulators in VGPRs (not AGPRs) so the update
 # kernel, whose lookahead block calls the ~250-VGPR diagonal factor, keeps 2 waves/SIMD; and
 # 16-byte LDS reads (ds_read_b128) for the factor's broadcast rows.
 EXTRA = {"chol.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form",
                       "-Xclang", "-target-feature", "-Xclang", "+enable-ds128"],
          # sobol.hip: the gathered LDS rows are read as 16-byte pairs
-         "sobol.hip": ["-Xclang", "-target-feature", "-Xclang", "+enable-ds128"]}
+         "sobol.hip": ["-Xclang", "-target-feature", "-Xclang", "+enable-ds128"],
+         # pcatrunc.hip: the epilogue reads every level's products with VALU instructions, so the
+         # MFMA accumulators live in VGPRs (no v_accvgpr_read per element and level)
+         "pcatrunc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 OBJ_DIR = os.path.join(PKG_DIR, "_obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -131,6 +131,12 @@ SIGNATURES = {
     "gp_xval": (c_int, [c_void_p, c_int, c_ll, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                         c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                         c_ll, c_void_p]),
+    "gp_pca_trunc_max_rank": (c_int, []),
+    "gp_pca_trunc_max_levels": (c_int, []),
+    "gp_pca_trunc_ws_bytes": (c_ll, [c_int, c_int, c_int]),
+    "gp_pca_trunc": (c_int, [c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                             c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_ll,
+                             c_void_p, c_ll, c_void_p]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

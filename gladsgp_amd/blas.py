@@ -6,6 +6,7 @@ logical shape and leading dimension so the GEMM call reads like BLAS.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -322,6 +323,112 @@ def field_score(W3: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = Non
                _ptr(hi), ldo, int(f32), rows.data_ptr(), _ptr(colt), ws.data_ptr(), nbytes,
                _stream(dev))
     return res
+
+
+def pca_trunc_limits():
+    """(largest rank, most levels per call) of gp_pca_trunc."""
+    lib = _capi.lib()
+    return int(lib.gp_pca_trunc_max_rank()), int(lib.gp_pca_trunc_max_levels())
+
+
+def _row_stride(fn, nm, t, rows, cols):
+    """Row stride of a 2-d operand with a unit column stride; a single row has none to check."""
+    if cols > 1 and t.stride(1) != 1:
+        raise ValueError(f"{fn}: {nm} needs a unit column stride (strides {t.stride()})")
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), cols, 1)
+    if ld < max(cols, 1):
+        raise ValueError(f"{fn}: {nm} needs a row stride >= its {cols} columns "
+                         f"(strides {t.stride()})")
+    return ld
+
+
+def pca_trunc(Y: torch.Tensor, C: torch.Tensor, V: torch.Tensor, ranks, mu=None, sd=None,
+              node: bool = False, out=None):
+    """Residual sums of the PCA truncation at every rank of ``ranks`` in one pass over the
+    ensemble (gp_pca_trunc): with e_r = (Y - mu) - sd (C[:, :ranks[r]] V[:ranks[r]]),
+    ``tot[r] = (sum e_r^2, sum e_r)`` and, when ``node``, ``node[r, j] = sum_i e_r[i, j]^2``.
+    Y (n, ncols) float32 or float64, C (n, p) = U diag(S) and V (p, ncols) float64, all on one HIP
+    device, row-major with free row strides; mu / sd (ncols) contiguous float64 or both None (0
+    and 1); ``ranks`` strictly increasing host integers within [0, min(p, the kernel's largest
+    rank)] (lists longer than the kernel's level limit are split over several calls: a level's
+    sums do not depend on the other levels).  Returns ``(tot, node_or_None)``, float64 device
+    tensors (R, 2) and (R, ncols); ``out`` = such a pair (node None when not requested, unit
+    column stride) to write into."""
+    fn = "pca_trunc"
+    for nm, t, dts in (("Y", Y, (torch.float32, F64)), ("C", C, (F64,)), ("V", V, (F64,))):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype not in dts:
+            raise ValueError(f"{fn}: {nm} must be a 2-d " +
+                             " or ".join(str(d).replace("torch.", "") for d in dts) + " tensor")
+    n, ncols = Y.shape
+    p = C.shape[1]
+    dev = Y.device
+    if C.device != dev or V.device != dev:
+        raise ValueError(f"{fn}: Y, C and V must be on one device")
+    if p < 1 or C.shape[0] != n or tuple(V.shape) != (p, ncols):
+        raise ValueError(f"{fn}: Y {tuple(Y.shape)} needs C (n x p) and V (p x ncols), got "
+                         f"C {tuple(C.shape)}, V {tuple(V.shape)}")
+    ldy = _row_stride(fn, "Y", Y, n, ncols)
+    ldc = _row_stride(fn, "C", C, n, p)
+    ldv = _row_stride(fn, "V", V, p, ncols)
+    if (mu is None) != (sd is None):
+        raise ValueError(f"{fn}: mu and sd go together")
+    for nm, t in (("mu", mu), ("sd", sd)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != F64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fn}: {nm} must be contiguous float64 on Y's device")
+        if t.numel() != ncols:
+            raise ValueError(f"{fn}: {nm} has {t.numel()} values, expected {ncols}")
+    try:
+        rk = [int(r) for r in np.asarray(ranks).reshape(-1)]
+        exact = bool(np.all(np.asarray(ranks).reshape(-1) == np.asarray(rk)))
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: ranks must be integers") from None
+    max_rank, max_lev = pca_trunc_limits()
+    if not exact or not rk or rk[0] < 0 or any(b <= a for a, b in zip(rk, rk[1:])):
+        raise ValueError(f"{fn}: ranks must be a non-empty strictly increasing list of "
+                         f"integers >= 0, got {list(np.asarray(ranks).reshape(-1))}")
+    if rk[-1] > min(p, max_rank):
+        raise ValueError(f"{fn}: rank {rk[-1]} is above the {p} columns of C or the kernel's "
+                         f"limit {max_rank}")
+    R = len(rk)
+    if out is None:
+        tot = torch.empty((R, 2), dtype=F64, device=dev)
+        nod = torch.empty((R, ncols), dtype=F64, device=dev) if node else None
+    else:
+        if len(out) != 2:
+            raise ValueError(f"{fn}: out is (tot, node)")
+        tot, nod = out
+        if not torch.is_tensor(tot) or tot.dtype != F64 or tot.device != dev or \
+                tuple(tot.shape) != (R, 2) or not tot.is_contiguous():
+            raise ValueError(f"{fn}: out[0] (tot) must be contiguous float64 of shape {(R, 2)} on "
+                             "Y's device")
+        if node != (nod is not None):
+            raise ValueError(f"{fn}: out[1] (node) is given exactly when node=True")
+        if nod is not None and (not torch.is_tensor(nod) or nod.dtype != F64 or
+                                nod.device != dev or tuple(nod.shape) != (R, ncols)):
+            raise ValueError(f"{fn}: out[1] (node) must be float64 of shape {(R, ncols)} on Y's "
+                             "device")
+    ldn = _row_stride(fn, "node", nod, R, ncols) if nod is not None else max(ncols, 1)
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: the operands must be on a HIP device")
+    if n == 0 or ncols == 0:                       # sums of nothing
+        tot.zero_()
+        if nod is not None:
+            nod.zero_()
+        return tot, nod
+    lib = _capi.lib()
+    for lo in range(0, R, max_lev):
+        part = rk[lo:lo + max_lev]
+        arr = (ctypes.c_int * len(part))(*part)
+        nbytes = int(lib.gp_pca_trunc_ws_bytes(n, ncols, len(part)))
+        ws = _ws(nbytes, dev)
+        _capi.call("gp_pca_trunc", Y.data_ptr(), ldy, int(Y.dtype == torch.float32), n, ncols,
+                   _ptr(mu), _ptr(sd), C.data_ptr(), ldc, V.data_ptr(), ldv,
+                   ctypes.addressof(arr), len(part), tot[lo:].data_ptr(),
+                   nod[lo:].data_ptr() if nod is not None else None, ldn, ws.data_ptr(), nbytes,
+                   _stream(dev))
+    return tot, nod
 
 
 def mean_var(x: torch.Tensor, ddof: int = 0):

@@ -598,6 +598,36 @@ int gp_xval(const double* Linv, int ldinv, long long strideInv, int n, const dou
             const double* shift, double* mean, double* var, int ldo, int* info, int batch,
             void* ws, long long ws_bytes, hipStream_t stream);
 
+/* PCA truncation-error curve: the residual sums of every requested truncation rank in one pass
+ * over the ensemble (plot_PC_RMSE.py:25-46,84-108: compute_truncation_error of the rank-k field
+ * U_k S_k Vh_k for each of 26 ranks; include_trunc_error.py:41-49: np.var of the same residual).
+ * With C = U diag(S) (n x pmax, row-major), V = Vh (pmax x ncols, row-major), pmax = ranks[nlev-1]:
+ *   e_r[i,j]       = (Y[i*ldy + j] - mu[j]) - sd[j] * sum_{k < ranks[r]} C[i*ldc + k] V[k*ldv + j]
+ *   tot[2r]        = sum_ij e_r^2          (RMSE = sqrt(tot[2r] / (n ncols)))
+ *   tot[2r+1]      = sum_ij e_r            (np.var = tot[2r]/N - (tot[2r+1]/N)^2, N = n ncols)
+ *   node[r*ldn + j] = sum_i e_r[i,j]^2     (node may be NULL)
+ * for r < nlev.  Y is float32 (y_f32 = 1, widened exactly as it is loaded: the reference's
+ * ensembles are float32 and are not copied) or fp64, row stride ldy >= ncols; everything else and
+ * all arithmetic is fp64.  mu and sd (ncols each) are NULL together: 0 and 1.
+ *   ranks  HOST array of nlev ints, 0 <= ranks[0] < ranks[1] < ... <= gp_pca_trunc_max_rank(),
+ *          nlev <= gp_pca_trunc_max_levels(); read at enqueue (a captured graph keeps the values).
+ *   ws     gp_pca_trunc_ws_bytes(n, ncols, nlev) bytes, 256-B aligned: 0 for an empty problem,
+ *          -1 for a negative size or nlev above the limit.
+ * Every level's sums are those of one k-ordered fp64 MFMA chain over k < ranks[r] per element (a
+ * level's values do not depend on which other levels are requested), reduced without atomics in
+ * an order fixed by (n, ncols) alone: equal inputs give equal bits, with or without node.
+ * Argument checks run on the host before any launch and return minus the argument's position:
+ * n, ncols, nlev and ranks first, then the other arguments in the order listed.  n = 0, ncols = 0
+ * or nlev = 0: validated, nothing launched, nothing written.  Stream-ordered, allocates nothing,
+ * can be captured into a hipGraph. */
+int gp_pca_trunc_max_rank(void);
+int gp_pca_trunc_max_levels(void);
+long long gp_pca_trunc_ws_bytes(int n, int ncols, int nlev);
+int gp_pca_trunc(const void* Y, long long ldy, int y_f32, int n, int ncols, const double* mu,
+                 const double* sd, const double* C, long long ldc, const double* V,
+                 long long ldv, const int* ranks, int nlev, double* tot, double* node,
+                 long long ldn, void* ws, long long ws_bytes, hipStream_t stream);
+
 /* out[0] = mean(x), out[1] = var(x, ddof) of a length-N vector (two-pass, deterministic);
  * work holds 1024 doubles.  np.var of the PC truncation residual, src/model.py:222. */
 int gp_mean_var(const double* x, long long N, int ddof, double* out, double* work,
