@@ -325,15 +325,26 @@ int gp_loglik_status(void* ws, int n, int batch, int reset, hipStream_t stream);
  * code; u the sweep's 2 ((d+1) P + 2 P + 1) uniforms, an update's proposal uniforms then its
  * acceptance uniforms, in update order; scratch 3 * GPFIT_MCMC_MAX_GROUP * P doubles) plus the
  * prior family / parameters / bounds and step type of each of betaU, lamUz, lamWs, lamWOs.
- * Update codes: 1..d betaU row, d+1 lamUz, d+2 lamWs, d+3 lamWOs.  For a group of g updates:
+ * Update codes: 1..d betaU row, d+1 lamUz, d+2 lamWs, d+3 lamWOs (code c reads u[2 P c ..]: P
+ * proposal then P acceptance uniforms; lamWOs one of each).  A code may appear at most once in
+ * a group.  A proposal outside [lo, hi] (a BetaRho one also: rho' outside (0, 1]) is rejected:
+ * its candidate is the current value.  An update is accepted when log(u_acc) < the difference
+ * of its log likelihood + log prior; a NaN difference (ll_all NaN, or -inf against -inf)
+ * rejects.  scratch holds three planes of GPFIT_MCMC_MAX_GROUP rows of P (candidates, in-range
+ * flags as 0 / 1, prior differences), row i = update i of the group prepared last (lamWOs:
+ * element 0 only); prep writes those rows and nothing else of it, decide reads them.  Only the
+ * accepted elements of the state and of ll, the counters of the group's codes (and of code 0
+ * when first != 0) and, when last != 0, lp are written.  For a group of g updates:
  *   gp_mcmc_group_prep   proposes them (first != 0: also the prior-only move of betaU row 0)
  *                        and writes the Gram inputs of the 2^g - 1 state sets, set
  *                        2^i - 1 + pat = update i proposed after the outcomes `pat` (bit q =
  *                        update q accepted) of updates 0..i-1, rows set * P + j of beta
  *                        (x d), s and delta: the batch for gp_loglik;
  *   gp_mcmc_group_decide takes the decisions in order from gp_loglik's ll_all (per GP; lamWOs
- *                        once on the sum), updates state, ll and counters in place and
- *                        (last != 0) writes the log posterior to lp;
+ *                        once on the sum over the GPs in index order, its outcome entering
+ *                        every GP's `pat`), updates state, ll and counters in place and
+ *                        (last != 0) writes the log posterior to lp: the sum over the GPs of
+ *                        ll + that GP's d + 3 log priors, plus lamWOs' log prior;
  *   gp_mcmc_group_step   gp_mcmc_group_decide of one group (S, kinds, g, last, ll_all) then
  *                        gp_mcmc_group_prep of the next (S_next, kinds_next, g_next, first,
  *                        beta, s, delta) in one launch (one kernel boundary less per group);

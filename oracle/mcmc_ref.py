@@ -10,7 +10,7 @@ un-vendored, ``requirements-cc.txt:55``, and unavailable offline — SURVEY sect
   ``Sigma_j = (1/lamUz_j) exp(-sum_k betaU[k+1,j] dt_k^2) + (1/lamWs_j + 1/(lamWOs LamSim_j)) I``
   (SURVEY A5/A7), via ``scipy.linalg.cholesky``;
 * log priors: Beta(a, b) on ``rho = exp(-beta/4)`` (rho clipped at 0.999), Gamma(a, b) as
-  (shape, rate);
+  (shape, rate), Normal(a, b) as (mean, standard deviation), Uniform (flat on the bounds);
 * proposals ``x + step (u - 1/2)`` (``BetaRho``: the same move on rho), out-of-bounds ->
   reject; accept when ``log u < delta log posterior``;
 * sweep order: betaU rows 0..d (row 0 = dummy x, prior only), lamUz, lamWs, lamWOs, with the
@@ -57,6 +57,10 @@ def log_prior(dist, params, x):
     if dist == "Beta":
         rho = np.minimum(np.exp(-x / 4.0), RHO_MAX)
         return (a - 1.0) * np.log(rho) + (b - 1.0) * np.log1p(-rho)
+    if dist == "Normal":                    # (mean, standard deviation)
+        return -0.5 * ((x - a) / b) ** 2
+    if dist == "Uniform":                   # flat on the bounds
+        return np.zeros_like(x)
     raise ValueError(dist)
 
 

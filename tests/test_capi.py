@@ -516,6 +516,52 @@ def test_mcmc_group_step_validates(lib):
                                   None) == -18
 
 
+def test_mcmc_group_prep_and_decide_validate(lib):
+    """gp_mcmc_group_prep / gp_mcmc_group_decide: every argument code, checked before the
+    launch (no pointer here is ever dereferenced)."""
+    from gladsgp_amd import _capi
+    S = _capi.McmcState()
+    for nm, _ in S._fields_[:14]:
+        setattr(S, nm, 64)
+    S.P, S.d = 4, 2
+    pS = ctypes.addressof(S)
+    k = (ctypes.c_int * 2)(1, 5)
+    dummy = ctypes.c_void_p(64)
+
+    def prep(S_=pS, kinds=k, g=2, beta=dummy, s=dummy, delta=dummy):
+        return lib.gp_mcmc_group_prep(S_, kinds, g, 0, beta, s, delta, None)
+
+    def decide(S_=pS, kinds=k, g=2, ll_all=dummy):
+        return lib.gp_mcmc_group_decide(S_, kinds, g, 1, ll_all, None)
+
+    for call in (prep, decide):
+        assert call(S_=None) == -1
+        for P, want in ((0, -2), (1025, -2), (1024, -7), (1, -7)):
+            S.P = P                                   # a valid P gets as far as the -7 below
+            assert (prep(beta=None) if call is prep else decide(ll_all=None)) == want, P
+        S.P = 4
+        for d, want in ((0, -3), (33, -3), (32, -7), (1, -6)):     # d = 1: code 5 > d + 3
+            S.d = d
+            assert (prep(beta=None) if call is prep else decide(ll_all=None)) == want, d
+        S.d = 2
+        k5 = (ctypes.c_int * 5)(1, 2, 3, 4, 5)
+        assert call(g=0) == -4
+        assert call(kinds=k5, g=5) == -4
+        assert call(kinds=None) == -4
+        for nm, _ in S._fields_[:14]:                 # each state pointer in turn
+            setattr(S, nm, None)
+            assert call() == -5, nm
+            setattr(S, nm, 64)
+        assert call(kinds=(ctypes.c_int * 2)(1, 0)) == -6
+        assert call(kinds=(ctypes.c_int * 2)(0, 1)) == -6
+        assert call(kinds=(ctypes.c_int * 2)(1, S.d + 4)) == -6
+        assert call(kinds=(ctypes.c_int * 1)(S.d + 4), g=1) == -6
+    assert prep(beta=None) == -7
+    assert prep(s=None) == -7
+    assert prep(delta=None) == -7
+    assert decide(ll_all=None) == -7
+
+
 def test_comm_argument_validation(lib):
     # RCCL wrappers: bad arguments are rejected before librccl is touched
     dummy = ctypes.c_void_p(16)

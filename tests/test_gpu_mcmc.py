@@ -80,13 +80,15 @@ def _spec(pr):
 def test_chain_matches_oracle(dev, n, d, P, steps_scale, graph, spec):
     """The oracle runs one update at a time; the sampler's speculative groups (spec updates per
     batched gp_loglik, 2^spec - 1 parameter states) must give the same chain."""
+    _chain_vs_oracle(dev, n, d, P, steps_scale, graph, spec, mcmc.ModelParams(d, P), 25)
+
+
+def _chain_vs_oracle(dev, n, d, P, steps_scale, graph, spec, pr, nsw):
     X, w, lam = _problem(n, d, P, seed=11 + n)
-    pr = mcmc.ModelParams(d, P)
     for k in pr.names:
         getattr(pr, k).mcmcStepParam = getattr(pr, k).mcmcStepParam * steps_scale
     sampler = mcmc.GPUSampler(_t(X, dev), _t(w, dev), _t(lam, dev), pr, use_graph=graph,
                               spec=spec)
-    nsw = 25
     rec = sampler.run(nsw, np.random.default_rng(5))
     U = np.random.default_rng(5).random((nsw, mcmc.uniforms_per_sweep(d, P)))
     state = {"betaU": pr.betaU.val, "lamUz": pr.lamUz.val[0], "lamWs": pr.lamWs.val[0],
@@ -97,6 +99,24 @@ def test_chain_matches_oracle(dev, n, d, P, steps_scale, graph, spec):
         np.testing.assert_allclose(rec[k], ref[k], rtol=1e-9, atol=1e-12, err_msg=k)
     assert acc["betaU"][1:].sum() > 0            # the chain actually moved
     assert np.all(np.isfinite(rec["logPost"]))
+    return sampler
+
+
+def test_chain_matches_oracle_multiwave_mixed_priors(dev):
+    """P = 70 GPs: a two-wave workgroup in the group kernels (the cross-wave hand-over of the
+    candidates and of the shared lamWOs decision), under Normal (lamUz), Uniform (lamWs), Gamma
+    (lamWOs) and Beta / BetaRho (betaU) priors."""
+    d, P = 3, 70
+    pr = mcmc.ModelParams(d, P)
+    pr.lamUz = mcmc.SepiaParam(1.0, "lamUz", (1, P), "Normal", [1.5, 1.0], [0.3, np.inf], 5.0,
+                               "Uniform")
+    pr.lamWs = mcmc.SepiaParam(1000.0, "lamWs", (1, P), "Uniform", [0.0, 1.0], [60.0, 1e5],
+                               100.0, "Uniform")
+    pr.mcmcList = [pr.betaU, pr.lamUz, pr.lamWs, pr.lamWOs]
+    sampler = _chain_vs_oracle(dev, 32, d, P, 1.0, True, 3, pr, 15)
+    assert sampler.fused
+    cnt = sampler.counts()
+    assert 0 < cnt["lamUz"].sum() < 15 * P and 0 < cnt["lamWs"].sum() < 15 * P
 
 
 def test_tune_and_sample(dev):
@@ -174,6 +194,26 @@ def test_fused_sweep_equals_tensor_sweep(dev, spec, graph):
                                   spec=spec, fused=fused)
         assert sampler.fused == fused
         recs.append(sampler.run(30, np.random.default_rng(13)))
+        cnts.append(sampler.counts())
+    for k in ("betaU", "lamUz", "lamWs", "lamWOs"):
+        np.testing.assert_array_equal(recs[1][k], recs[0][k], err_msg=k)
+    np.testing.assert_allclose(recs[1]["logPost"], recs[0]["logPost"], rtol=1e-13, atol=0)
+    for k in cnts[0]:
+        np.testing.assert_array_equal(cnts[1][k], cnts[0][k], err_msg=str(k))
+
+
+def test_fused_sweep_equals_tensor_sweep_multiwave(dev):
+    """The same at P = 70 (two waves per workgroup), spec 3: the fused sweep's chain and counters
+    equal the tensor-op sweep's."""
+    n, d, P = 32, 3, 70
+    X, w, lam = _problem(n, d, P, seed=71)
+    recs, cnts = [], []
+    for fused in (False, True):
+        pr = mcmc.ModelParams(d, P)
+        sampler = mcmc.GPUSampler(_t(X, dev), _t(w, dev), _t(lam, dev), pr, use_graph=False,
+                                  spec=3, fused=fused)
+        assert sampler.fused == fused
+        recs.append(sampler.run(15, np.random.default_rng(13)))
         cnts.append(sampler.counts())
     for k in ("betaU", "lamUz", "lamWs", "lamWOs"):
         np.testing.assert_array_equal(recs[1][k], recs[0][k], err_msg=k)
