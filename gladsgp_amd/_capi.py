@@ -137,6 +137,15 @@ SIGNATURES = {
     "gp_pca_trunc": (c_int, [c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                              c_ll, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_ll,
                              c_void_p, c_ll, c_void_p]),
+    "gp_alpha_ws_bytes": (c_ll, [c_int, c_int]),
+    "gp_alpha": (c_int, [c_void_p, c_int, c_ll, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                         c_void_p, c_ll, c_void_p]),
+    "gp_mean_response_max_grid": (c_int, []),
+    "gp_mean_response_max_int_elems": (c_int, []),
+    "gp_mean_response": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                 c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                 c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_ll,
+                                 c_void_p]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

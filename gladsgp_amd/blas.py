@@ -136,7 +136,8 @@ def field(W: torch.Tensor, K: torch.Tensor, sd: torch.Tensor | None = None,
     (ncols) or both None (standardised field), err (rows) or None; Y (rows x ncols) float32 when
     ``f32`` else float64."""
     rows, P = W.shape
-    if K.shape[0] != P or K.stride(1) != 1 or W.stride(1) != 1:
+    # (a dimension of one element has no stride to check: the reference's scalar models, P = ny = 1)
+    if K.shape[0] != P or (K.shape[1] > 1 and K.stride(1) != 1) or (P > 1 and W.stride(1) != 1):
         raise ValueError("field: W (rows x P) and K (P x ncols) must be row-major, K.shape[0] = P")
     ncols = K.shape[1]
     if out is None:

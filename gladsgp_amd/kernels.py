@@ -490,6 +490,164 @@ def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True
     return mean, var
 
 
+_ALPHA_WS = {}
+RESP_ORDER = {"cyclic": 0, "ascending": 1}     # GPFIT_RESP_CYCLIC / GPFIT_RESP_ASCENDING
+RESP_MAX_EFFECTS = 64                          # GPFIT_RESP_MAX_EFFECTS
+
+
+def alpha(chol: Cholesky, w, out: torch.Tensor | None = None) -> torch.Tensor:
+    """alpha = A^-1 w = L^-T (L^-1 w) per problem -> (batch, n) (gp_alpha): the weights of the
+    posterior mean, which :func:`mean_response` contracts.  ``w`` a contiguous float64
+    (batch, n) device tensor; ``out`` a float64 (batch, n) tensor with unit column stride."""
+    if not isinstance(chol, Cholesky):
+        raise ValueError("chol: expected a kernels.Cholesky (padded L^-1)")
+    L = chol.linv_buf
+    dev, batch, n = L.device, L.shape[0], chol.n
+    npad = padded_n(n)
+    if not torch.is_tensor(w) or w.dtype != F64:
+        raise ValueError("w: expected a float64 tensor")
+    if w.dim() == 1:
+        w = w.reshape(1, -1)
+    if tuple(w.shape) != (batch, n):
+        raise ValueError(f"w: expected shape ({batch}, {n}), got {tuple(w.shape)}")
+    if not w.is_contiguous():
+        raise ValueError("w: expected a contiguous tensor")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != F64 or tuple(out.shape) != (batch, n) or \
+                (n > 1 and out.stride(1) != 1) or (batch > 1 and out.stride(0) < n):
+            raise ValueError(f"out: expected a float64 ({batch}, {n}) tensor with unit column "
+                             "stride")
+    if L.dtype != F64 or tuple(L.shape) != (batch, npad, npad) or not L.is_contiguous():
+        raise ValueError(f"chol: expected a contiguous float64 ({batch}, {npad}, {npad}) L^-1")
+    for t, nm in ((L, "chol"), (w, "w")) + (((out, "out"),) if out is not None else ()):
+        _check_device(t, nm)
+    if out is None:
+        out = torch.empty((batch, n), dtype=F64, device=dev)
+    if n == 0 or batch == 0:
+        return out
+    nbytes = int(_capi.lib().gp_alpha_ws_bytes(n, batch))
+    ws = _ALPHA_WS.setdefault(str(dev), Workspace()).get(nbytes, dev)
+    _capi.call("gp_alpha", L.data_ptr(), npad, npad * npad, n, w.data_ptr(), n, out.data_ptr(),
+               out.stride(0) if batch > 1 else n, batch, ws.data_ptr(), ws.numel(), _stream(dev))
+    return out
+
+
+def mean_response_max_grid() -> int:
+    return int(_capi.lib().gp_mean_response_max_grid())
+
+
+def mean_response_max_int_elems() -> int:
+    return int(_capi.lib().gp_mean_response_max_int_elems())
+
+
+def _f64_tensor(t, name: str, shape_txt: str, ok) -> None:
+    if not torch.is_tensor(t) or t.dtype != F64:
+        raise ValueError(f"{name}: expected a float64 tensor")
+    if not ok(t):
+        raise ValueError(f"{name}: expected shape {shape_txt}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor")
+
+
+def mean_response(X, alpha, beta, s, effects, t1, t2=None, Xint=None, order: str = "ascending",
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Mean-response surfaces of ``batch`` GPs in closed form (gp_mean_response): for every effect
+    the posterior mean at x_d1 = t1[a1] (and x_d2 = t2[a2]) averaged over the integration points
+    ``Xint`` placed in the other dimensions.  Returns (batch, E, T1) for main effects,
+    (batch, E, T2, T1) for pairs.
+
+    ``X`` (n, d), ``alpha`` (batch, n) from :func:`alpha`, ``beta`` (batch, d), ``s`` (batch,),
+    ``t1`` (T1,), ``t2`` (T2,), ``Xint`` (I, d - nfree): contiguous float64 device tensors.
+    ``effects``: a sequence of dimensions (main effects) or of (d1, d2) pairs, on the host; more
+    than 64 are split over several calls.  ``order``: "cyclic" (integration column c takes
+    dimension (d1 + 1 + c) mod d; main effects only) or "ascending" (the non-free dimensions in
+    ascending order).  ``Xint`` may be None when every dimension is free (d == nfree).  ``out``:
+    a contiguous float64 tensor of the result's shape."""
+    _f64_tensor(X, "X", "(n, d)", lambda t: t.dim() == 2 and t.shape[1] >= 1)
+    n, d = X.shape
+    _f64_tensor(alpha, "alpha", f"(batch, {n})", lambda t: t.dim() == 2 and t.shape[1] == n)
+    batch = alpha.shape[0]
+    _f64_tensor(beta, "beta", f"({batch}, {d})", lambda t: tuple(t.shape) == (batch, d))
+    _f64_tensor(s, "s", f"({batch},)", lambda t: tuple(t.shape) == (batch,))
+    try:
+        eff = np.asarray(effects)
+        if eff.size and not np.issubdtype(eff.dtype, np.integer):
+            if not np.all(eff == np.floor(eff)):
+                raise ValueError
+        eff = eff.astype(np.int64)
+    except (TypeError, ValueError):
+        raise ValueError("effects: expected a sequence of dimensions or of (d1, d2) pairs") \
+            from None
+    if eff.ndim == 0 or eff.ndim > 2 or (eff.ndim == 2 and eff.shape[1] not in (1, 2)):
+        raise ValueError("effects: expected a sequence of dimensions or of (d1, d2) pairs")
+    nfree = 1 if eff.ndim == 1 else int(eff.shape[1])
+    eff = eff.reshape(-1, nfree)
+    E = eff.shape[0]
+    if ((eff < 0) | (eff >= d)).any():
+        raise ValueError(f"effects: a dimension lies outside [0, {d})")
+    if nfree == 2 and (eff[:, 0] == eff[:, 1]).any():
+        raise ValueError("effects: a pair frees one dimension twice")
+    if order not in RESP_ORDER:
+        raise ValueError(f"order: expected 'cyclic' or 'ascending', got {order!r}")
+    if order == "cyclic" and nfree == 2:
+        raise ValueError("order: 'cyclic' is the main effects' rule; pairs take 'ascending'")
+    tmax = mean_response_max_grid()
+    _f64_tensor(t1, "t1", f"(T1,) with 1 <= T1 <= {tmax}",
+                lambda t: t.dim() == 1 and 1 <= t.numel() <= tmax)
+    T1, T2 = t1.numel(), 1
+    if nfree == 2:
+        if t2 is None:
+            raise ValueError("t2: pairs need the second dimension's targets")
+        _f64_tensor(t2, "t2", f"(T2,) with 1 <= T2 <= {tmax}",
+                    lambda t: t.dim() == 1 and 1 <= t.numel() <= tmax)
+        T2 = t2.numel()
+    elif t2 is not None:
+        raise ValueError("t2: main effects take t1 only")
+    nc = d - nfree
+    if nc < 0:
+        raise ValueError(f"effects: pairs need d >= 2, got d = {d}")
+    I = 0
+    if nc > 0:
+        if Xint is None:
+            raise ValueError(f"Xint: expected the (I, {nc}) integration points")
+        _f64_tensor(Xint, "Xint", f"(I, {nc}) with I >= 1",
+                    lambda t: t.dim() == 2 and t.shape[1] == nc and t.shape[0] >= 1)
+        I = Xint.shape[0]
+        if I * nc > mean_response_max_int_elems():
+            raise ValueError(f"Xint: {I} x {nc} values exceed "
+                             f"gp_mean_response_max_int_elems() = {mean_response_max_int_elems()}")
+    elif Xint is not None:
+        raise ValueError("Xint: every dimension is free, there is nothing to integrate")
+    shape = (batch, E, T1) if nfree == 1 else (batch, E, T2, T1)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != F64 or tuple(out.shape) != shape or \
+                not out.is_contiguous():
+            raise ValueError(f"out: expected a contiguous float64 {shape} tensor")
+    ops = [(X, "X"), (alpha, "alpha"), (beta, "beta"), (s, "s"), (t1, "t1")]
+    ops += [(t, nm) for t, nm in ((t2, "t2"), (Xint, "Xint"), (out, "out")) if t is not None]
+    for t, nm in ops:
+        _check_device(t, nm)
+    dev = X.device
+    if out is None:
+        out = torch.empty(shape, dtype=F64, device=dev)
+    if n == 0:
+        return out.zero_()
+    if batch == 0 or E == 0:
+        return out
+    import ctypes
+    TT = T1 * T2
+    for e0 in range(0, E, RESP_MAX_EFFECTS):
+        ne = min(E - e0, RESP_MAX_EFFECTS)
+        host = (ctypes.c_int * (ne * nfree))(*[int(v) for v in eff[e0:e0 + ne].reshape(-1)])
+        _capi.call("gp_mean_response", X.data_ptr(), n, d, d, alpha.data_ptr(), n,
+                   beta.data_ptr(), d, s.data_ptr(), batch, ctypes.addressof(host), nfree, ne,
+                   RESP_ORDER[order], t1.data_ptr(), T1,
+                   t2.data_ptr() if t2 is not None else None, T2,
+                   Xint.data_ptr() if Xint is not None else None, I, max(nc, 1),
+                   out.data_ptr() + 8 * e0 * TT, TT, E * TT, _stream(dev))
+    return out
+
+
 @dataclass
 class Prepared:
     """Cross-covariance of every test-point chunk, built by :func:`predict_prepare`."""

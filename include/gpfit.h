@@ -609,6 +609,68 @@ int gp_xval(const double* Linv, int ldinv, long long strideInv, int n, const dou
             const double* shift, double* mean, double* var, int ldo, int* info, int batch,
             void* ws, long long ws_bytes, hipStream_t stream);
 
+/* alpha_b = A_b^-1 w_b = Linv_b^T (Linv_b w_b) from the L^-1 of gp_potrf_inv: the weights of the
+ * posterior mean, mean(x) = sum_n alpha_n k(x, x_n), which gp_mean_response contracts in closed
+ * form (the reference never forms them: mean_response.py:126,200 predict point by point).
+ *   Linv   the padded L^-1 of gp_potrf_inv under gp_xval's layout rules: ldinv >= gp_padded_n(n),
+ *          strideInv >= ldinv * gp_padded_n(n), any naturally aligned layout (a 16-B aligned base
+ *          with even ldinv and strideInv selects 16-B loads); column c is taken as zero above
+ *          row c and below row n - 1 whatever the buffer holds there.
+ *   w      n values at w + b * ldw;  alpha: n values written at alpha + b * lda.
+ *   ws     gp_alpha_ws_bytes(n, batch) bytes, 256-B aligned (z = L^-1 w of every problem; -1 for
+ *          a negative size).
+ * Two launches per 65535 problems: z by the masked triangular gemv, then one wave per column for
+ * sum_{k >= i} L^-1[k,i] z_k (fixed order: equal inputs give equal bits).  Stream-ordered,
+ * allocates nothing, can be captured into a hipGraph.  n = 0 or batch = 0: no launch.  A
+ * violation returns minus its argument position before anything is launched. */
+long long gp_alpha_ws_bytes(int n, int batch);
+int gp_alpha(const double* Linv, int ldinv, long long strideInv, int n, const double* w, int ldw,
+             double* alpha, int lda, int batch, void* ws, long long ws_bytes, hipStream_t stream);
+
+/* Mean-response surfaces of the posterior mean: main effects (nfree = 1) and input pairs
+ * (nfree = 2), the GP arithmetic of mean_response.py's compute_mean_response (lines 82-138:
+ * per input dimension 11 targets x 20 Latin-hypercube integration points predicted and averaged)
+ * and compute_mean_response_pairs (lines 159-208: one SepiaEmulatorPrediction of 10 points per
+ * node of an 11 x 11 grid).  The kernel is a product over dimensions, so with alpha of gp_alpha
+ * the average over the integration points has a closed form and no test point is materialised.
+ * Per problem b and effect e, freeing d1 = effects[e*nfree] (and d2 = effects[e*nfree + 1]):
+ *   M_n = (1/I) sum_i exp(-sum_{k not free} beta_b[k] (X[n,k] - Xint[i*ldi + col(k)])^2)
+ *   out[b*ldb + e*lde + a2*T1 + a1] = s[b] sum_n alpha_b[n] M_n
+ *          exp(-beta_b[d1] (X[n,d1] - t1[a1])^2) exp(-beta_b[d2] (X[n,d2] - t2[a2])^2)
+ * (the d2 factor and a2 absent when nfree = 1): the posterior mean at x_d1 = t1[a1],
+ * x_d2 = t2[a2] averaged over the I integration points placed in the other dimensions.
+ *   effects  HOST array of E * nfree ints, read at enqueue (a captured graph keeps the values);
+ *            d1 != d2, both in [0, d), in either order; E <= GPFIT_RESP_MAX_EFFECTS.
+ *   order    which dimension integration column c takes: GPFIT_RESP_CYCLIC (d1 + 1 + c) mod d
+ *            (compute_mean_response's dnums rule, nfree = 1 only), GPFIT_RESP_ASCENDING the
+ *            non-free dimensions in ascending order (compute_mean_response_pairs's dim_int).
+ *   t1, t2   T1 / T2 device values, 1 <= T <= gp_mean_response_max_grid(); t2 / T2 are ignored
+ *            when nfree = 1 (T2 is taken as 1).
+ *   Xint     device, row-major I x (d - nfree), row stride ldi >= d - nfree, I >= 1 and
+ *            I (d - nfree) <= gp_mean_response_max_int_elems() (kept in LDS).  d == nfree:
+ *            nothing to integrate, M_n = 1, Xint may be NULL and I is ignored.
+ *   alpha    n values at alpha + b * lda;  X, beta, s, ldx, ldbeta as for gp_gram_ardse.
+ *   out      lde >= T1 T2, ldb >= (E - 1) lde + T1 T2; nothing else of out is written.
+ * One workgroup per (problem, effect); fp64 throughout, no atomics, one summation order fixed by
+ * (n, I, T1, T2): equal inputs give equal bits, and the value of (b, e) does not depend on batch,
+ * on E or on the other effects requested.  The error of a value is bounded by a small multiple of
+ * eps s sum_n |alpha_n| M_n E1 E2: it scales with |alpha|, i.e. with the conditioning of A
+ * ("Mean-response surfaces").  Stream-ordered, allocates nothing, can be captured into
+ * a hipGraph.  E = 0, batch = 0 or n = 0: validated, nothing launched, nothing written.  A
+ * violation returns minus its argument position (1 = X ... 24 = ldb) before any launch: a bad
+ * effect -11, E above the limit -13, GPFIT_RESP_CYCLIC with nfree = 2 -14. */
+#define GPFIT_RESP_CYCLIC 0      /* integration column c -> dimension (d1 + 1 + c) mod d     */
+#define GPFIT_RESP_ASCENDING 1   /* integration columns -> the non-free dimensions, ascending */
+#define GPFIT_RESP_MAX_EFFECTS 64
+int gp_mean_response_max_grid(void);        /* 64 */
+int gp_mean_response_max_int_elems(void);   /* 2048: largest I * (d - nfree) kept in LDS */
+int gp_mean_response(const double* X, int n, int d, int ldx, const double* alpha, int lda,
+                     const double* beta, int ldbeta, const double* s, int batch,
+                     const int* effects, int nfree, int E, int order,
+                     const double* t1, int T1, const double* t2, int T2,
+                     const double* Xint, int I, int ldi,
+                     double* out, long long lde, long long ldb, hipStream_t stream);
+
 /* PCA truncation-error curve: the residual sums of every requested truncation rank in one pass
  * over the ensemble (plot_PC_RMSE.py:25-46,84-108: compute_truncation_error of the rank-k field
  * U_k S_k Vh_k for each of 26 ranks; include_trunc_error.py:41-49: np.var of the same residual).
