@@ -165,7 +165,16 @@ SIGNATURES = {
     "gp_set_poll_budget": (c_ll, [c_ll]),
     "gp_set_potrf_path": (c_int, [c_int]),
     "gp_set_predict_path": (c_int, [c_int]),
+    "gp_pp_schedule_host": (c_ll, [c_int, c_int, c_int, c_void_p, c_ll]),
+    "gp_pp_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gp_pp_plan_stream": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gp_pp_schedule_ws_bytes": (c_ll, [c_int, c_int, c_int]),
+    "gp_pp_schedule": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p]),
 }
+
+# GP_PP_PLAN_*: the words of gp_pp_plan's report
+PP_PLAN = ("eligible", "N", "lead", "kPPLead", "kPPLeadBlocked", "kPPXDelay", "kPPMaxN",
+           "groups", "grid", "tasks", "resident", "nkeys")
 
 PROF_GRAM, PROF_POTRF, PROF_TRMM, PROF_CROSS = 0, 1, 2, 3
 LINV_PADDED, LINV_PACKED = 0, 1        # GPFIT_LINV_PADDED / GPFIT_LINV_PACKED

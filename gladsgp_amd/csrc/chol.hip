@@ -1944,6 +1944,9 @@ constexpr int kPPXDelay = 8;   // XT tasks: 8 chain steps after the late LT task
 //   late   (K = t - 4W)  XT(i,c): K = 4i+2 + 4XD;  LT(i,j), i-j > kPPBand: K = 2(i+j)
 // Every input of a late task has a smaller key or is a chain step whose own inputs do (see the
 // section comment).  Shared by the schedule kernel (count + emit) and the host's task count.
+// tests/test_pp_sched_cpu.py checks the order (completeness, no task waiting on one not yet
+// dequeued at W = 0, at most kPPLeadBlocked of them at kPPLead) against a dependence model on
+// the CPU: run it after any change here.
 template <typename F>
 GP_HD inline void pp_for_key(int t, int N, bool inv, int lead, int xd, F&& f) {
   if (inv && t < kPPZKeys) {
@@ -2131,7 +2134,7 @@ static int pp_lead(int batch, int resident) {
 // hand each other and re-read (every L_jk of a row, D_j) are served by that XCD's L2 instead of
 // being fetched once per XCD from the Infinity Fabric.  Placement is a speed assumption only:
 // each queue is a problem-closed, per-problem topological list served by grid / 8 workgroups,
-// and the deadlock argument of pp_schedule_kernel holds per queue (pp_lead / pp_eligible scaled
+// and the deadlock argument of pp_schedule_kernel holds per queue (pp_lead / pp_plan's test scaled
 // by 8 are the same inequalities).  Not for batch 1 (C3): one problem on one XCD would leave
 // seven idle.
 static int pp_groups(int batch, int grid) {
@@ -2145,6 +2148,10 @@ struct PPScratch {
   int fstride;
   size_t task_bytes, flag_bytes;
   size_t bytes() const { return task_bytes + flag_bytes; }
+  // the three parts of a scratch at `scr` (gp_pp_schedule's header comment documents them)
+  int2* tasks(char* scr) const { return reinterpret_cast<int2*>(scr); }
+  int* head(char* scr) const { return reinterpret_cast<int*>(scr + task_bytes); }
+  int* flags(char* scr) const { return reinterpret_cast<int*>(scr + task_bytes + 256); }
 };
 
 static PPScratch pp_scratch(int n, int batch, bool inv) {
@@ -2162,32 +2169,60 @@ static bool pp_shape_ok(int n, int batch) {
   return N <= kPPMaxN && pp_task_count(N, true) * (long long)batch < (1ll << 30);
 }
 
-static bool pp_eligible(int n, int batch, int resident) {
+// What one persistent factorisation of (n, batch, inv) launches on `resident` workgroup slots:
+// the one place that decides eligibility, grid, dequeue lead and queues, for the entry points,
+// pp_factor and the gp_pp_plan hook alike (tests/test_pp_sched_cpu.py checks this rule against a
+// dependence model of the task list).  `lead` >= 0 replaces pp_lead's choice (hooks only).
+struct PPPlan {
+  bool eligible;
+  int N, lead, groups, grid;     // (0 where the shape is beyond the persistent kernel)
+  PPScratch s;                   // s.ntasks = batch x (tasks per problem + its chain entry)
+};
+
+static PPPlan pp_plan(int n, int batch, bool inv, int resident, int lead = -1) {
+  PPPlan pl{};
+  pl.N = gp_ceil_div(n, NB);
+  const bool shape = pp_shape_ok(n, batch);
   // the chains hold `batch` workgroups for the whole launch: at least as many workers again
-  return g_potrf_path != 1 && pp_shape_ok(n, batch) && 2 * batch <= resident;
+  pl.eligible = g_potrf_path != 1 && shape && 2 * batch <= resident;
+  if (!shape) return pl;
+  pl.s = pp_scratch(n, batch, inv);
+  pl.grid = (int)(pl.s.ntasks < resident ? pl.s.ntasks : resident);
+  pl.lead = lead >= 0 ? lead : pp_lead(batch, pl.grid);
+  pl.groups = pp_groups(batch, pl.grid);
+  return pl;
+}
+
+// The schedule launch of (N, batch, inv, lead) into the scratch `scr` laid out by `s`: the task
+// list, and head, flags, info and logdet zeroed (pp_factor and the gp_pp_schedule hook).
+static int pp_launch_schedule(const PPScratch& s, char* scr, int N, int batch, bool inv,
+                              int lead, int* info, double* logdet, int preset_abort,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(pp_schedule_kernel, dim3(pp_schedule_grid(batch)), dim3(1024), 0, stream,
+                     s.tasks(scr), N, batch, inv ? 1 : 0, lead, kPPXDelay, s.head(scr),
+                     256 / (int)sizeof(int), info, logdet, s.flags(scr), s.fstride,
+                     preset_abort);
+  GP_CK(hipGetLastError());
+  return 0;
 }
 
 // The persistent dataflow factorisation (pp_kernel) on `stream` in the caller's scratch `scr`
-// (pp_scratch bytes, 256-B aligned): one schedule launch, one persistent launch with one
-// workgroup per resident slot.  p.X is L^-1 (inv, zeroed by the caller) or the 64 x 64N D_k
-// scratch (ldx = 64).  `ll`: gp_loglik's in-chain mode (gpfit_potrf_loglik), pp_kernel<true>.
-static int pp_factor(const Problem& p, bool inv, char* scr, int resident, hipStream_t stream,
-                     GpfitPre pre = GpfitPre(), hipEvent_t ev_launch = nullptr,
-                     const PPLoglik* ll = nullptr) {
+// (pp_scratch bytes, 256-B aligned) as `plan` (pp_plan of the same n, batch, inv) lays it out:
+// one schedule launch, one persistent launch with one workgroup per resident slot.  p.X is L^-1
+// (inv, zeroed by the caller) or the 64 x 64N D_k scratch (ldx = 64).  `ll`: gp_loglik's
+// in-chain mode (gpfit_potrf_loglik), pp_kernel<true>.
+static int pp_factor(const Problem& p, bool inv, char* scr, const PPPlan& plan,
+                     hipStream_t stream, GpfitPre pre = GpfitPre(),
+                     hipEvent_t ev_launch = nullptr, const PPLoglik* ll = nullptr) {
   const int n = p.n, batch = p.batch;
-  const int N = gp_ceil_div(n, NB);
-  const PPScratch s = pp_scratch(n, batch, inv);
-  const int grid = (int)(s.ntasks < resident ? s.ntasks : resident);
-  int2* tasks = reinterpret_cast<int2*>(scr);
-  int* head = reinterpret_cast<int*>(scr + s.task_bytes);
-  int* flags = reinterpret_cast<int*>(scr + s.task_bytes + 256);
-  const int lead = pp_lead(batch, grid);
+  const int N = plan.N;
+  const PPScratch& s = plan.s;
+  const int grid = plan.grid;
   const long long budget = g_poll_budget;
   // the schedule kernel also zeroes head + flags and info / logdet
-  hipLaunchKernelGGL(pp_schedule_kernel, dim3(pp_schedule_grid(batch)), dim3(1024), 0, stream,
-                     tasks, N, batch, inv ? 1 : 0, lead, kPPXDelay, head, 256 / (int)sizeof(int),
-                     p.info, p.logdet, flags, s.fstride, budget < 0 ? 1 : 0);
-  GP_CK(hipGetLastError());
+  const int src = pp_launch_schedule(s, scr, N, batch, inv, plan.lead, p.info, p.logdet,
+                                     budget < 0 ? 1 : 0, stream);
+  if (src) return src;
   if (pre.fn) {
     const int prc = pre.fn(pre.arg);
     if (prc) return prc;
@@ -2203,9 +2238,9 @@ static int pp_factor(const Problem& p, bool inv, char* scr, int resident, hipStr
   P.plain = (p.lda % 16 == 0) && (p.ldx % 16 == 0) && al128(p.A) && al128(p.X) &&
             (batch == 1 || (p.sA % 16 == 0 && p.sX % 16 == 0));
   P.budget = budget > 0 ? budget : kPollBudget;
-  P.tasks = tasks; P.ntasks = (int)s.ntasks;
-  P.groups = pp_groups(batch, grid);
-  P.head = head; P.flags = flags; P.fstride = s.fstride;
+  P.tasks = s.tasks(scr); P.ntasks = (int)s.ntasks;
+  P.groups = plan.groups;
+  P.head = s.head(scr); P.flags = s.flags(scr); P.fstride = s.fstride;
 #ifdef GPFIT_PP_TRACE
   P.dbg = g_trace_dbg;
   P.trace = g_trace_buf;
@@ -2291,8 +2326,8 @@ int gpfit_potrf_inv_event(double* A, int n, int lda, long long strideA, double* 
   if (n == 0 || batch == 0) return pre.fn ? pre.fn(pre.arg) : 0;
   const Problem p{A, lda, strideA, Linv, ldinv, strideInv, n, batch, info, logdet};
   const int npad = gp_padded_n(n);
-  const int resident = pp_resident(stream);
-  const bool pp = pp_eligible(n, batch, resident);
+  const PPPlan plan = pp_plan(n, batch, true, pp_resident(stream));
+  const bool pp = plan.eligible;
   if (pp) {
     if (!ws || !ws_aligned(ws)) return -11;
     if (ws_bytes < gpfit_potrf_inv_ws_bytes(n, batch)) return -12;
@@ -2314,7 +2349,7 @@ int gpfit_potrf_inv_event(double* A, int n, int lda, long long strideA, double* 
     // waits on it runs beside the whole factorisation, not beside the Gram),
     // one asked for at k_ev >= N after it
     const int N = gp_ceil_div(n, NB);
-    rc = pp_factor(p, true, static_cast<char*>(ws), resident, stream, pre,
+    rc = pp_factor(p, true, static_cast<char*>(ws), plan, stream, pre,
                    (ev && k_ev >= 0 && k_ev < N) ? ev : nullptr);
     if (rc == 0 && ev && !(k_ev >= 0 && k_ev < N)) GP_CK(hipEventRecord(ev, stream));
   } else {
@@ -2333,8 +2368,8 @@ int gpfit_potrf_loglik(double* G, int n, long long strideG, double* D, long long
                        const double* w, int ldw, double* zb, int zld, double* zz, int batch,
                        int* info, double* logdet, double* ll, int* status, int* info_out,
                        void* ws, long long ws_bytes, hipStream_t stream, GpfitPre pre) {
-  const int resident = pp_resident(stream);
-  if (!pp_eligible(n, batch, resident)) return 1;   // the caller's L^-1 path
+  const PPPlan plan = pp_plan(n, batch, false, pp_resident(stream));
+  if (!plan.eligible) return 1;   // the caller's L^-1 path
   if (!ws || !ws_aligned(ws)) return -11;
   if (ws_bytes < gpfit_potrf_loglik_ws_bytes(n, batch)) return -12;
   const int N = gp_ceil_div(n, NB);
@@ -2344,7 +2379,7 @@ int gpfit_potrf_loglik(double* G, int n, long long strideG, double* D, long long
   // (the profiler's POTRF pair brackets the Gram `pre` too on this path: it is enqueued
   // between the schedule kernel and pp_kernel; the fit's roofline subtracts nothing for it)
   gpfit_prof_begin(GP_PROF_POTRF, stream);
-  const int rc = pp_factor(p, false, static_cast<char*>(ws), resident, stream, pre, nullptr, &L);
+  const int rc = pp_factor(p, false, static_cast<char*>(ws), plan, stream, pre, nullptr, &L);
   gpfit_prof_end(GP_PROF_POTRF, stream);
   return rc;
 }
@@ -2390,8 +2425,8 @@ extern "C" int gp_potrf_ws(double* A, int n, int lda, long long strideA, int bat
   if (n == 0 || batch == 0) return 0;
   if (!ws || !ws_aligned(ws)) return -8;
   if (ws_bytes < gp_potrf_ws_bytes(n, batch)) return -9;
-  const int resident = pp_resident(stream);
-  const bool pp = pp_eligible(n, batch, resident);
+  const PPPlan plan = pp_plan(n, batch, false, pp_resident(stream));
+  const bool pp = plan.eligible;
   if (!pp) {   // (pp_factor's schedule kernel zeroes them)
     if (info) GP_CK(hipMemsetAsync(info, 0, sizeof(int) * batch, stream));
     if (logdet) GP_CK(hipMemsetAsync(logdet, 0, sizeof(double) * batch, stream));
@@ -2400,7 +2435,7 @@ extern "C" int gp_potrf_ws(double* A, int n, int lda, long long strideA, int bat
   const Problem p{A, lda, strideA, static_cast<double*>(ws), NB, potrf_d_stride(n), n, batch,
                   info, logdet};
   char* scr = static_cast<char*>(ws) + potrf_d_bytes(n, batch);
-  return pp ? pp_factor(p, false, scr, resident, stream)
+  return pp ? pp_factor(p, false, scr, plan, stream)
             : potrf_sweep<kPotrf>(p, stream, -1, nullptr);
 }
 
@@ -2455,6 +2490,99 @@ extern "C" int gp_set_potrf_path(int path) {
   const int prev = g_potrf_path;
   g_potrf_path = (path == 1 || path == 2) ? path : 0;
   return prev;
+}
+
+// ---- Schedule diagnostics (test hooks; include/gpfit.h) -----------------------------------------
+
+// The tasks of one problem in the order pp_schedule_kernel emits them (no HIP call).
+extern "C" long long gp_pp_schedule_host(int n, int inv, int lead, int* out, long long cap) {
+  if (n < 1 || gp_ceil_div(n, NB) > kPPMaxN) return -1;
+  if (inv != 0 && inv != 1) return -2;
+  if (lead < 0 || lead > 8) return -3;
+  if (cap < 0) return -5;
+  if (cap > 0 && !out) return -4;
+  const int N = gp_ceil_div(n, NB);
+  long long c = 0;
+  for (int t = 0; t < pp_nkeys(N, lead, kPPXDelay); ++t)
+    pp_for_key(t, N, inv != 0, lead, kPPXDelay, [&](int kind, int i, int j) {
+      if (c < cap) {
+        out[3 * c] = kind;
+        out[3 * c + 1] = i;
+        out[3 * c + 2] = j;
+      }
+      ++c;
+    });
+  return c;
+}
+
+static int pp_plan_args(int n, int batch, int inv) {
+  if (n < 1) return -1;
+  if (batch < 1) return -2;
+  if (inv != 0 && inv != 1) return -3;
+  return 0;
+}
+
+static void pp_plan_report(const PPPlan& pl, int batch, int resident, long long* out) {
+  out[GP_PP_PLAN_ELIGIBLE] = pl.eligible ? 1 : 0;
+  out[GP_PP_PLAN_N] = pl.N;
+  out[GP_PP_PLAN_LEAD] = pl.lead;
+  out[GP_PP_PLAN_KLEAD] = kPPLead;
+  out[GP_PP_PLAN_KLEAD_BLOCKED] = kPPLeadBlocked;
+  out[GP_PP_PLAN_KXDELAY] = kPPXDelay;
+  out[GP_PP_PLAN_KMAXN] = kPPMaxN;
+  out[GP_PP_PLAN_GROUPS] = pl.groups;
+  out[GP_PP_PLAN_GRID] = pl.grid;
+  out[GP_PP_PLAN_TASKS] = pl.grid ? pl.s.ntasks / batch - 1 : 0;
+  out[GP_PP_PLAN_RESIDENT] = resident;
+  out[GP_PP_PLAN_NKEYS] = pp_nkeys(pl.N, pl.lead, kPPXDelay);
+}
+
+extern "C" int gp_pp_plan(int n, int batch, int inv, int resident, int lead, long long* out) {
+  const int arc = pp_plan_args(n, batch, inv);
+  if (arc) return arc;
+  if (resident < 1) return -4;
+  if (lead < -1 || lead > 8) return -5;
+  if (!out) return -6;
+  pp_plan_report(pp_plan(n, batch, inv != 0, resident, lead), batch, resident, out);
+  return 0;
+}
+
+extern "C" int gp_pp_plan_stream(int n, int batch, int inv, int lead, long long* out,
+                                 hipStream_t stream) {
+  const int arc = pp_plan_args(n, batch, inv);
+  if (arc) return arc;
+  if (lead < -1 || lead > 8) return -4;
+  if (!out) return -5;
+  const int resident = pp_resident(stream);
+  pp_plan_report(pp_plan(n, batch, inv != 0, resident, lead), batch, resident, out);
+  return 0;
+}
+
+static int pp_schedule_args(int n, int batch, int inv) {
+  if (n < 1 || gp_ceil_div(n, NB) > kPPMaxN) return -1;
+  if (batch < 1 || !pp_shape_ok(n, batch)) return -2;
+  if (inv != 0 && inv != 1) return -3;
+  return 0;
+}
+
+extern "C" long long gp_pp_schedule_ws_bytes(int n, int batch, int inv) {
+  const int arc = pp_schedule_args(n, batch, inv);
+  if (arc) return arc;
+  return (long long)pp_scratch(n, batch, inv != 0).bytes();
+}
+
+// pp_schedule_kernel alone, through pp_factor's launch helper.
+extern "C" int gp_pp_schedule(int n, int batch, int inv, int lead, void* ws, long long ws_bytes,
+                              hipStream_t stream) {
+  const int arc = pp_schedule_args(n, batch, inv);
+  if (arc) return arc;
+  const int N = gp_ceil_div(n, NB);
+  if (lead < 0 || lead > 8 || pp_nkeys(N, lead, kPPXDelay) > 1024) return -4;
+  if (!ws || !ws_aligned(ws)) return -5;
+  const PPScratch s = pp_scratch(n, batch, inv != 0);
+  if (ws_bytes < (long long)s.bytes()) return -6;
+  return pp_launch_schedule(s, static_cast<char*>(ws), N, batch, inv != 0, lead, nullptr, nullptr,
+                            0, stream);
 }
 
 #ifdef GPFIT_PP_TRACE

@@ -785,6 +785,76 @@ long long gp_set_poll_budget(long long polls);
  * kernel with one shared task queue for every batch.  Returns the previous setting. */
 int gp_set_potrf_path(int path);
 
+/*
+ * Test hooks: the persistent factorisation's task schedule, so that its order and the launch
+ * rule can be checked without running a factorisation (tests/test_pp_sched_cpu.py checks them
+ * against a dependence model, tests/test_gpu_pp_sched.py the device's list against the host's).
+ * A task is (kind, i, j) on the 64 x 64 tiles of one problem, N = ceil(n / 64) tile rows:
+ */
+#define GP_PP_TASK_CHAIN 0  /* list entries only: the problem's chain (diagonal + subdiagonal)   */
+#define GP_PP_TASK_LT 1     /* L tile (i, j), i >= j + 2                                         */
+#define GP_PP_TASK_DP 2     /* partial sums of diagonal tile j (i = 0)                           */
+#define GP_PP_TASK_SP 3     /* partial sums of subdiagonal tile (i, j), i = j + 1                */
+#define GP_PP_TASK_XT 4     /* L^-1 tile (i, j), i > j                                           */
+#define GP_PP_TASK_Z 5      /* zero the L^-1 tiles (r, i), r = j .. min(j + 8, i) - 1            */
+#define GP_PP_TASK_XT2 6    /* L^-1 tiles (i, j) and (i, j + 1), i > j + 1                       */
+#define GP_PP_TASK_ZP 7     /* zero the padding tile row N, tile columns i .. i + 7 (j = 0)      */
+
+/*
+ * gp_pp_schedule_host: the tasks of one problem of order n (inv = 1: with L^-1) in the order
+ * the schedule kernel emits them with dequeue lead `lead` (0 .. 8), the chain entry not
+ * included: task t as out[3t .. 3t+2] = (kind, i, j), for the first `cap` tasks.  Returns the
+ * number of tasks (cap = 0: the size to allocate), the same for every lead.  Makes no HIP call.
+ * n beyond the persistent kernel's range (n > 64 * 240) returns -1.
+ */
+long long gp_pp_schedule_host(int n, int inv, int lead, int* out, long long cap);
+
+/*
+ * gp_pp_plan: what a factorisation of (n, batch, inv) enqueued on a stream with `resident`
+ * persistent workgroup slots would launch, from the same function the entry points use
+ * (gp_set_potrf_path applies).  lead = -1: the library's own dequeue lead; 0 .. 8: that one
+ * instead.  out[GP_PP_PLAN_*], GP_PP_PLAN_NUM words.  Makes no HIP call.  n beyond the
+ * persistent kernel's range is no error: ELIGIBLE = 0 and GROUPS, GRID, TASKS are 0.
+ * gp_pp_plan_stream is the same with `resident` taken from `stream` (its CU mask and the
+ * persistent kernel's occupancy on the current device), reported in out[GP_PP_PLAN_RESIDENT].
+ */
+#define GP_PP_PLAN_ELIGIBLE 0      /* 1: the persistent kernel runs; 0: the blocked sweep        */
+#define GP_PP_PLAN_N 1             /* tile rows, ceil(n / 64)                                    */
+#define GP_PP_PLAN_LEAD 2          /* dequeue lead of this launch: 0 or KLEAD (or the given one) */
+#define GP_PP_PLAN_KLEAD 3         /* the library's lead where the rule allows one               */
+#define GP_PP_PLAN_KLEAD_BLOCKED 4 /* the rule's bound on blocked tasks per problem at KLEAD     */
+#define GP_PP_PLAN_KXDELAY 5       /* chain steps the L^-1 tasks are dequeued behind their row   */
+#define GP_PP_PLAN_KMAXN 6         /* largest N of the persistent kernel                         */
+#define GP_PP_PLAN_GROUPS 7        /* dequeue queues: 1, or 8 (queue g: list entries 8k + g)     */
+#define GP_PP_PLAN_GRID 8          /* workgroups launched                                        */
+#define GP_PP_PLAN_TASKS 9         /* tasks per problem, its chain entry not counted             */
+#define GP_PP_PLAN_RESIDENT 10     /* the residency the plan was made for                        */
+#define GP_PP_PLAN_NKEYS 11        /* schedule keys (one schedule-kernel thread each, <= 1024)   */
+#define GP_PP_PLAN_NUM 12
+int gp_pp_plan(int n, int batch, int inv, int resident, int lead, long long* out);
+int gp_pp_plan_stream(int n, int batch, int inv, int lead, long long* out, hipStream_t stream);
+
+/*
+ * gp_pp_schedule: enqueues the schedule kernel alone, as a factorisation of (n, batch, inv)
+ * with dequeue lead `lead` (0 .. 8) does ahead of its persistent launch, into the 256-byte
+ * aligned scratch `ws` of gp_pp_schedule_ws_bytes(n, batch, inv) bytes (the persistent part of
+ * gp_potrf_inv_ws_bytes / gp_potrf_ws_bytes), and writes nothing past that size.  Needs n <=
+ * 64 * 240.  Scratch layout, with T = out[GP_PP_PLAN_TASKS] tasks per problem:
+ *   task list   batch * (T + 1) entries of two 32-bit ints, (kind | b << 4, i | j << 16) for
+ *               problem b: first the batch chain entries (b = 0 .. batch-1), then each of the T
+ *               tasks of gp_pp_schedule_host's order in turn for b = 0 .. batch-1; padded to a
+ *               multiple of 256 bytes
+ *   header      256 bytes, the dequeue counters: all 0 after the schedule kernel
+ *   flag words  batch * fstride ints, fstride = 2 N^2 + 2 N + 1 rounded up to a multiple of 32:
+ *               all 0 after the schedule kernel; padded to a multiple of 256 bytes
+ * An invalid argument returns minus its position before any launch (-1: n, -2: batch, also a
+ * task list of 2^30 entries or more, -3: inv, -4: lead, -5: ws null or not 256-byte aligned,
+ * -6: ws_bytes too small).
+ */
+long long gp_pp_schedule_ws_bytes(int n, int batch, int inv);
+int gp_pp_schedule(int n, int batch, int inv, int lead, void* ws, long long ws_bytes,
+                   hipStream_t stream);
+
 /* A-B hook, process-wide: the prediction path of gp_predict / gp_predict_ex / gp_fit_predict /
  * gp_predict_solve enqueued afterwards.  0 = automatic (at gp_padded_n(n) <= 512 the
  * column-resident kernel, the cross-covariance produced inside it when d <= 8 and read from

@@ -608,6 +608,56 @@ def test_factorisation_workspace_entry_points(lib):
     assert lib.gp_loglik_status(wsp, 0, 1, 0, None) == 0
 
 
+def test_schedule_hooks_return_codes(lib):
+    """gp_pp_schedule_host / gp_pp_plan / gp_pp_plan_stream / gp_pp_schedule_ws_bytes /
+    gp_pp_schedule: minus the argument's position, in argument order, before any launch (no row
+    here passes validation of an entry point that would launch or query the device)."""
+    from gladsgp_amd import _capi
+    wsp, ws16 = ctypes.c_void_p(256), ctypes.c_void_p(16)
+    top = 64 * 240
+    out3 = (ctypes.c_int * 3)()
+    host = lib.gp_pp_schedule_host
+    for args, rc in [((0, 1, 0, out3, 1), -1), ((top + 1, 1, 0, out3, 1), -1),
+                     ((0, 2, 9, None, -1), -1), ((64, 2, 0, out3, 1), -2),
+                     ((64, -1, 9, None, -1), -2), ((64, 1, -1, out3, 1), -3),
+                     ((64, 1, 9, None, -1), -3), ((64, 1, 8, None, 1), -4),
+                     ((64, 1, 8, None, -1), -5), ((64, 1, 8, out3, -1), -5),
+                     ((64, 1, 8, None, 0), 2), ((64, 0, 0, None, 0), 0),
+                     ((64, 1, 8, out3, 1), 2)]:
+        assert host(*args) == rc, args
+    out = (ctypes.c_longlong * len(_capi.PP_PLAN))()
+    plan = lib.gp_pp_plan
+    for args, rc in [((0, 1, 1, 256, -1, out), -1), ((0, 0, 2, 0, 9, None), -1),
+                     ((64, 0, 1, 256, -1, out), -2), ((64, 0, 2, 0, 9, None), -2),
+                     ((64, 1, 2, 256, -1, out), -3), ((64, 1, -1, 0, 9, None), -3),
+                     ((64, 1, 1, 0, -1, out), -4), ((64, 1, 1, 0, 9, None), -4),
+                     ((64, 1, 1, 256, -2, out), -5), ((64, 1, 1, 256, 9, None), -5),
+                     ((64, 1, 1, 256, -1, None), -6), ((64, 1, 1, 256, 8, out), 0),
+                     ((top + 1, 1, 1, 256, -1, out), 0), ((1 << 30, 1 << 30, 0, 1, 0, out), 0)]:
+        assert plan(*args) == rc, args
+    assert len(_capi.PP_PLAN) == 12 and list(out)[:2] == [0, 1 << 24]       # not eligible, N
+    for args, rc in [((0, 1, 1, -1, out, None), -1), ((64, 0, 1, -1, out, None), -2),
+                     ((64, 1, 2, -1, out, None), -3), ((64, 1, 1, -2, out, None), -4),
+                     ((64, 1, 1, 9, None, None), -4), ((64, 1, 1, -1, None, None), -5)]:
+        assert lib.gp_pp_plan_stream(*args) == rc, args
+    size = lib.gp_pp_schedule_ws_bytes
+    for args, rc in [((0, 1, 1), -1), ((top + 1, 0, 2), -1), ((64, 0, 1), -2), ((64, 0, 2), -2),
+                     ((top, 1 << 20, 1), -2), ((64, 1, 2), -3), ((64, 1, -1), -3)]:
+        assert size(*args) == rc, args
+    assert size(64, 1, 0) == 256 + 512 and size(top, 8, 1) == lib.gp_potrf_inv_ws_bytes(top, 8)
+    sched = lib.gp_pp_schedule
+    big = 1 << 40
+    for args, rc in [((0, 1, 1, 0, wsp, big, None), -1), ((top + 1, 0, 2, 9, None, 0, None), -1),
+                     ((64, 0, 1, 0, wsp, big, None), -2), ((top, 1 << 20, 2, 9, None, 0, None), -2),
+                     ((64, 1, 2, 0, wsp, big, None), -3), ((64, 1, -1, 9, None, 0, None), -3),
+                     ((64, 1, 1, -1, wsp, big, None), -4), ((64, 1, 1, 9, None, 0, None), -4),
+                     ((64, 1, 1, 0, None, big, None), -5), ((64, 1, 1, 0, ws16, big, None), -5),
+                     ((64, 1, 1, 0, None, 0, None), -5),
+                     ((64, 1, 1, 0, wsp, size(64, 1, 1) - 1, None), -6),
+                     ((top, 8, 1, 8, wsp, size(top, 8, 1) - 1, None), -6)]:
+        assert sched(*args) == rc, args
+
+
 def _kernel_resources():
     """Per-kernel register and LDS use read from the built library's gfx950 code objects
     (offload bundles -> AMDGPU metadata note, printed by llvm-readelf)."""
