@@ -375,21 +375,13 @@ namespace {
 //       contiguous runs.
 // The operands' element types are template parameters (float32 X read as stored and widened
 // exactly, as the general kernel does), so float32 and fp64 operands give the same bits.
-#ifndef TSK_WAVES
-#define TSK_WAVES 4
-#endif
-constexpr int kTskWaves = TSK_WAVES;           // waves per tsk block, 64 rows each
+constexpr int kTskWaves = 4;                   // waves per tsk block, 64 rows each
 constexpr int kTskRows = 64 * kTskWaves;       // rows of C per tsk block
 constexpr int kTskMinK = 1 << 16;
 // 256 rows (4 waves x 64) at two blocks per CU: 0.53-0.56 of HBM on the fit's products, against
 // 0.42-0.47 at 128 x 3, 0.29-0.31 at 64 x 4, 0.48-0.49 at 512 x 1 (profiles/r05/r05w_tsm*.log)
-#ifndef TSM_ROWS
-#define TSM_ROWS 256
-#endif
-#ifndef TSM_OCC
-#define TSM_OCC 2
-#endif
-constexpr int kTsmRows = TSM_ROWS;   // rows of the big dimension per tsm block
+constexpr int kTsmRows = 256;    // rows of the big dimension per tsm block
+constexpr int kTsmOcc = 2;       // blocks per CU (launch_bounds' waves per SIMD at 4 waves)
 constexpr int kTsmMaxK = 1024;   // K of a tsm product (the number of runs)
 constexpr int kTsMaxN = 32;          // narrow side (two 16-wide MFMA column tiles)
 
@@ -507,7 +499,7 @@ __global__ __launch_bounds__(64 * kTskWaves, 8 / kTskWaves) void gemm_tsk_kernel
 // L2: 100 KB at the fit's 512 x 25), C(i, j) = C[i*ci + j*cj].  The block's rows are written
 // through LDS as runs along whichever of i / j is contiguous in C.
 template <typename EP, typename EQ>
-__global__ __launch_bounds__(256, TSM_OCC) void gemm_tsm_kernel(int M, int N, int K,
+__global__ __launch_bounds__(256, kTsmOcc) void gemm_tsm_kernel(int M, int N, int K,
                                                           const EP* __restrict__ P, int ldp,
                                                           const EQ* __restrict__ Q, long long qk,
                                                           long long qj, double alpha,

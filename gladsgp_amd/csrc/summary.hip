@@ -5,12 +5,11 @@
 // builds only to reduce it (four test points at a time, because it does not fit otherwise) is
 // never stored: 3 m ny outputs instead of S m ny.
 //
-// Layout: block = 4 waves; every wave owns 32 consecutive columns (two 16-column MFMA tiles),
-// the block 128.  A work unit is (column panel, test point); block i takes a contiguous range of
-// the panel-major unit list and keeps its K panel (the B operands of all k-steps) in registers
-// while the panel lasts, as field_kernel does.  The point's S rows of w (one per sample, stride
-// lds) stream through LDS in 32-sample tiles (16 at P > 32), double-buffered across unit
-// boundaries (the next tile's global loads in flight under the current tile's MFMAs); the
+// Layout (field_core.h, shared with field.hip): block = 4 waves; every wave owns 32 consecutive
+// columns (two 16-column MFMA tiles), the block 128.  A work unit is (column panel, test point);
+// block i takes a contiguous range of the panel-major unit list and keeps its K panel in
+// registers while the panel lasts.  The point's S rows of w (one per sample, stride lds) stream
+// through LDS in 32-sample tiles (16 at P > 32), double-buffered across unit boundaries; the
 // tile's error scalars ride in a spare column of the LDS rows.
 //
 // After a tile's MFMAs every lane folds its 2 x 8 accumulator values (MFMA C layout: lane l,
@@ -24,8 +23,9 @@
 // tails (one keeps the lower list, the other the upper), so each of the 64 lanes ends with one
 // complete list of one column and does one interpolation.  No LDS is needed for the merge.
 //
-// Bits: a_s is field_kernel's k-ordered MFMA chain (same operands, same order), y and z are the
-// same fma / add as its epilogue, so every sample value equals gp_field's bit for bit; the order
+// Bits: a_s is field_kernel's k-ordered MFMA chain (same operands, same order: tested directly by
+// tests/test_gpu_summary.py::test_one_sample_is_the_field), y and z are the same fma / add as
+// field_kernel's epilogue, so every sample value equals gp_field's bit for bit; the order
 // statistics are selections of those values (exact), the interpolation is numpy's _lerp with its
 // three roundings (no contraction), the mean is a fixed-order fp64 sum divided by S.
 //
@@ -33,28 +33,21 @@
 // (summary_body<KS, KT, SCORE>, see there): row and column partial sums into a workspace, added in
 // a fixed order by score_reduce_kernel.  summary_kernel<KS, KT> is the SCORE = false instance and
 // compiles to the registers, LDS and scratch it had as a kernel of its own.
-#include "gpfit_common.h"
+#include "field_core.h"
 #include "../../include/gpfit.h"
 
 #include <math.h>
 
 namespace {
 
+using namespace field_core;
+
 // waves per SIMD the register allocator is asked to keep: 2 (256 registers per lane; the small
 // instantiations end below that and fit 3-4); the deepest lists (2 x 2 x 8 doubles of state
 // beside the K panel) get the whole file instead of spilling to scratch
 template <int KS, int KT> constexpr int sum_occ() { return KT > 4 || (KT == 4 && KS > 12) ? 1 : 2; }
-constexpr int kSumWaves = 4;                  // waves per block
-constexpr int kSumJT = 2;                     // 16-column MFMA tiles per wave
-constexpr int kSumThreads = 64 * kSumWaves;
-constexpr int kSumWaveCols = 16 * kSumJT;
-constexpr int kSumCols = kSumWaves * kSumWaveCols;   // output columns per block
-// samples per tile: 32 (two 16-row MFMA sub-tiles), 16 at P > 32 where the K panel (128 of the
-// 256 registers at P = 64) leaves no room for the second sub-tile's accumulators and staging
-template <int KS> constexpr int sum_rows() { return KS <= 8 ? 32 : 16; }
-constexpr int kSumPitch = 68;                 // LDS row pitch of a w tile (doubles)
-constexpr int kSumErrCol = 64;                // the row's error scalar (k < 64 are the weights)
-constexpr int kSumMaxP = 64;
+constexpr int kSumErrCol = kMaxP;             // the row's error scalar (k < kMaxP: the weights)
+static_assert(kSumErrCol < kPitch, "the error scalar rides inside the LDS row");
 constexpr int kSumMaxTail = 8;
 
 // one tail of the band: the two list positions numpy's linear rule reads and its weight
@@ -100,7 +93,7 @@ struct ScoreK {
   int y_f32;
   double floor;
   double* rowp;   // 8 doubles per unit (GPFIT_SCORE_ROW_* order)
-  double* colp;   // per segment 4 x kSumCols doubles (GPFIT_SCORE_COL_* order); may be null
+  double* colp;   // per segment 4 x kCols doubles (GPFIT_SCORE_COL_* order); may be null
 };
 
 // the lower lane's terms of one element: (mu - y)^2 and |(mu - y) / y|, every operation rounded
@@ -130,10 +123,8 @@ GP_DEV void summary_body(
     const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
     void* __restrict__ mean, void* __restrict__ lo, void* __restrict__ hi, long long ldo,
     int out_f32, int nts, const ScoreK& sc) {
-  constexpr int KP = 4 * KS;                               // padded inner dimension
-  constexpr int kSumRows = sum_rows<KS>(), RS = kSumRows / 16;
-  constexpr int NLD = (kSumRows * KP + kSumThreads - 1) / kSumThreads;   // per thread
-  __shared__ double ws[2][kSumRows * kSumPitch];
+  constexpr int kRows = tile_rows<KS>(), RS = kRows / 16;
+  __shared__ double ws[2][kRows * kPitch];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int li = lane & 15, lk = lane >> 4;
   // SCORE: the lane's column accumulator (lower lane: sum of squared residuals and valid count,
@@ -142,80 +133,82 @@ GP_DEV void summary_body(
   [[maybe_unused]] int col_n = 0, rp = 0;
   [[maybe_unused]] double* rsh = nullptr;
   if constexpr (SCORE) {
-    __shared__ double row_sh[2][kSumWaves][8];
+    __shared__ double row_sh[2][kWaves][8];
     rsh = &row_sh[0][0][0];
   }
   // the finished unit's row partial: the four waves' sums in wave order
   [[maybe_unused]] auto flush_row = [&](long long unit) {
     if (threadIdx.x < 8) {
-      const double* r = rsh + rp * (kSumWaves * 8) + threadIdx.x;
+      const double* r = rsh + rp * (kWaves * 8) + threadIdx.x;
       sc.rowp[unit * 8 + threadIdx.x] = ((r[0] + r[8]) + r[16]) + r[24];
     }
     rp ^= 1;
   };
   [[maybe_unused]] auto flush_cols = [&](long long pan) {
     if (sc.colp) {
-      const int idx = wv * kSumWaveCols + 16 * (lk & 1) + li;
-      double* seg = sc.colp + ((long long)blockIdx.x + pan) * (4 * kSumCols) + idx;
+      const int idx = wv * kWaveCols + 16 * (lk & 1) + li;
+      double* seg = sc.colp + ((long long)blockIdx.x + pan) * (4 * kCols) + idx;
       const bool upl = lk >> 1;
-      seg[(upl ? 3 : 0) * kSumCols] = col_s;
-      seg[(upl ? 2 : 1) * kSumCols] = (double)col_n;
+      seg[(upl ? 3 : 0) * kCols] = col_s;
+      seg[(upl ? 2 : 1) * kCols] = (double)col_n;
     }
     col_s = 0.0;
     col_n = 0;
   };
-  const long long npanels = (ncols + kSumCols - 1) / kSumCols;
+  const long long npanels = (ncols + kCols - 1) / kCols;
   const long long units = npanels * m;
   const long long u0 = units * blockIdx.x / gridDim.x;
   const long long u1 = units * (blockIdx.x + 1) / gridDim.x;
   if (u0 >= u1) return;                                    // block-uniform
   const double inf = __builtin_inf();
 
-  double b[KS][kSumJT];
+  double b[KS][kJT];
   long long cur = -1;                                      // the panel held in b
+  // (panel load, tile load / store and chain are field.hip's, written out: see the note there)
   auto load_panel = [&](long long panel) {
-    const int c0 = (int)panel * kSumCols + wv * kSumWaveCols;   // this wave's first column
+    const int c0 = (int)panel * kCols + wv * kWaveCols;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-      for (int jt = 0; jt < kSumJT; ++jt) {
+      for (int jt = 0; jt < kJT; ++jt) {
         const int k = 4 * ks + lk, c = c0 + 16 * jt + li;
         b[ks][jt] = (k < P && c < ncols) ? K[(long long)k * ldk + c] : 0.0;
       }
     cur = panel;
   };
 
-  // tile ts of point i -> registers: element e = tid + 256 q is (sample row e / KP, k e % KP);
-  // the first kSumRows threads also fetch their row's error scalar
+  // tile ts of point i (sample rows, stride lds) -> registers; the first kRows threads also
+  // fetch their row's error scalar
+  constexpr int KP = 4 * KS, NLD = tile_loads<KS>();        // padded inner dimension
   double pre[NLD], pre_e = -0.0;
-  auto load_tile = [&](int i, int ts) {
-    const int s0 = ts * kSumRows;
+  auto fetch_tile = [&](int i, int ts) {
+    const int s0 = ts * kRows;
     const double* wp = W + (long long)i * ldw;
 #pragma unroll
     for (int q = 0; q < NLD; ++q) {
-      const int e = threadIdx.x + kSumThreads * q;
+      const int e = threadIdx.x + kThreads * q;
       const int r = e / KP, k = e % KP;
-      pre[q] = (e < kSumRows * KP && k < P && s0 + r < S) ? wp[(long long)(s0 + r) * lds + k]
-                                                          : 0.0;
+      pre[q] = (e < kRows * KP && k < P && s0 + r < S) ? wp[(long long)(s0 + r) * lds + k]
+                                                     : 0.0;
     }
-    if (err && threadIdx.x < kSumRows)
+    if (err && threadIdx.x < kRows)
       pre_e = s0 + (int)threadIdx.x < S ? err[(long long)(s0 + (int)threadIdx.x) * m + i] : -0.0;
   };
-  auto store_tile = [&](int buf) {
+  auto stage_tile = [&](int buf) {
 #pragma unroll
     for (int q = 0; q < NLD; ++q) {
-      const int e = threadIdx.x + kSumThreads * q;
-      if (e < kSumRows * KP) ws[buf][(e / KP) * kSumPitch + e % KP] = pre[q];
+      const int e = threadIdx.x + kThreads * q;
+      if (e < kRows * KP) ws[buf][(e / KP) * kPitch + e % KP] = pre[q];
     }
-    if (threadIdx.x < kSumRows) ws[buf][threadIdx.x * kSumPitch + kSumErrCol] = pre_e;
+    if (threadIdx.x < kRows) ws[buf][threadIdx.x * kPitch + kSumErrCol] = pre_e;
   };
 
   // running state of the lane's two columns (tile jt, column li): rows lk + 4 q of every tile
-  double sum[kSumJT], lo_l[kSumJT][KT], nh_l[kSumJT][KT], s_c[kSumJT], m_c[kSumJT];
+  double sum[kJT], lo_l[kJT][KT], nh_l[kJT][KT], s_c[kJT], m_c[kJT];
   auto reset = [&](long long panel) {
-    const int c0 = (int)panel * kSumCols + wv * kSumWaveCols;
+    const int c0 = (int)panel * kCols + wv * kWaveCols;
 #pragma unroll
-    for (int jt = 0; jt < kSumJT; ++jt) {
+    for (int jt = 0; jt < kJT; ++jt) {
       sum[jt] = 0.0;
 #pragma unroll
       for (int i = 0; i < KT; ++i) lo_l[jt][i] = nh_l[jt][i] = inf;
@@ -229,8 +222,8 @@ GP_DEV void summary_body(
 
   long long u = u0, panel = u0 / m;                        // unit u = panel * m + i
   int i = (int)(u0 - panel * m), ts = 0, buf = 0;
-  load_tile(i, 0);
-  store_tile(0);
+  fetch_tile(i, 0);
+  stage_tile(0);
   __syncthreads();
   reset(panel);
   for (;;) {
@@ -243,25 +236,25 @@ GP_DEV void summary_body(
       in = i + 1 == m ? 0 : i + 1;
     }
     const bool more = un < u1;
-    if (more) load_tile(in, tsn);                          // in flight under the MFMAs
-    f64x4 acc[RS][kSumJT];
+    if (more) fetch_tile(in, tsn);                         // in flight under the MFMAs
+    f64x4 acc[RS][kJT];
 #pragma unroll
     for (int rs = 0; rs < RS; ++rs)
 #pragma unroll
-      for (int jt = 0; jt < kSumJT; ++jt) acc[rs][jt] = zero4();
+      for (int jt = 0; jt < kJT; ++jt) acc[rs][jt] = zero4();
     const double* wt = ws[buf];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
       for (int rs = 0; rs < RS; ++rs) {
-        const double a = wt[(16 * rs + li) * kSumPitch + 4 * ks + lk];
+        const double a = wt[(16 * rs + li) * kPitch + 4 * ks + lk];
 #pragma unroll
-        for (int jt = 0; jt < kSumJT; ++jt)
+        for (int jt = 0; jt < kJT; ++jt)
           acc[rs][jt] = mfma16x16x4(a, b[ks][jt], acc[rs][jt]);
       }
     }
     // fold: sample row 16 rs + lk + 4 q of the tile, column 16 jt + li of the wave's panel
-    const int s0 = ts * kSumRows;
+    const int s0 = ts * kRows;
     // (without err the scalar is -0: a + -0 = a for every a, as fma(a, 1, -0) = a without sd --
     // one code path for all four operand combinations keeps the register budget).
     // Rows past S are masked by the branch: their lanes execute none of the fold.
@@ -271,9 +264,9 @@ GP_DEV void summary_body(
       for (int q = 0; q < 4; ++q) {
         const int r = 16 * rs + lk + 4 * q;
         if (s0 + r < S) {
-          const double e = wt[r * kSumPitch + kSumErrCol];
+          const double e = wt[r * kPitch + kSumErrCol];
 #pragma unroll
-          for (int jt = 0; jt < kSumJT; ++jt) {
+          for (int jt = 0; jt < kJT; ++jt) {
             const double a = acc[rs][jt][q];
             const double y = fma(a, s_c[jt], m_c[jt]);
             const double z = fma(a + e, s_c[jt], m_c[jt]);
@@ -290,7 +283,7 @@ GP_DEV void summary_body(
       const bool odd = lk & 1, up = lk >> 1;
       [[maybe_unused]] double yv = __builtin_nan("");      // stays NaN: no truth for this element
       if constexpr (SCORE) {
-        const int c = (int)panel * kSumCols + wv * kSumWaveCols + 16 * (int)odd + li;
+        const int c = (int)panel * kCols + wv * kWaveCols + 16 * (int)odd + li;
         if (sc.Y && c < ncols) {                           // in flight under the merge
           const long long o = (long long)i * sc.ldy + c;
           yv = sc.y_f32 ? (double)static_cast<const float*>(sc.Y)[o]
@@ -337,7 +330,7 @@ GP_DEV void summary_body(
         vb = -vb;
       }
       const double qv = sum_lerp(va, vb, t);
-      const int c = (int)panel * kSumCols + wv * kSumWaveCols + 16 * (int)odd + li;
+      const int c = (int)panel * kCols + wv * kWaveCols + 16 * (int)odd + li;
       if constexpr (!SCORE) {
         if (c < ncols) {
           const long long o = (long long)i * ldo + c;
@@ -397,7 +390,7 @@ GP_DEV void summary_body(
           tc += __shfl_xor(tc, d);
           tn += __shfl_xor(tn, d);
         }
-        double* r = rsh + (rp * kSumWaves + wv) * 8;
+        double* r = rsh + (rp * kWaves + wv) * 8;
         if (lane == 0) {
           r[0] = ta;
           r[1] = (double)(tn & 255);
@@ -419,7 +412,7 @@ GP_DEV void summary_body(
       }
       break;
     }
-    store_tile(buf ^ 1);                                   // the other buffer: last read a tile ago
+    stage_tile(buf ^ 1);                                   // the other buffer: last read a tile ago
     __syncthreads();
     buf ^= 1;
     if (tsn == 0) {
@@ -437,7 +430,7 @@ GP_DEV void summary_body(
 }
 
 template <int KS, int KT>
-__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kernel(
+__global__ __launch_bounds__(kThreads, (sum_occ<KS, KT>())) void summary_kernel(
     const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
     const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
     const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
@@ -448,7 +441,7 @@ __global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void summary_kern
 }
 
 template <int KS, int KT>
-__global__ __launch_bounds__(kSumThreads, (sum_occ<KS, KT>())) void score_kernel(
+__global__ __launch_bounds__(kThreads, (sum_occ<KS, KT>())) void score_kernel(
     const double* __restrict__ W, long long ldw, long long lds, int S, int m, int P,
     const double* __restrict__ K, long long ldk, int ncols, const double* __restrict__ sd,
     const double* __restrict__ mu, const double* __restrict__ err, SumTail tlo, SumTail thi,
@@ -490,15 +483,15 @@ __global__ __launch_bounds__(256) void score_reduce_kernel(
   }
   const long long c = (long long)(blockIdx.x - m) * 256 + threadIdx.x;
   if (c >= ncols) return;
-  const long long p = c / kSumCols, units = npanels * m;
-  const int idx = (int)(c % kSumCols);
+  const long long p = c / kCols, units = npanels * m;
+  const int idx = (int)(c % kCols);
   const long long b0 = score_block_of(p * m, units, grid);
   const long long b1 = score_block_of(p * m + m - 1, units, grid);
   double a[4] = {0.0, 0.0, 0.0, 0.0};
   for (long long b = b0; b <= b1; ++b) {
-    const double* seg = colp + (b + p) * (4 * kSumCols) + idx;
+    const double* seg = colp + (b + p) * (4 * kCols) + idx;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] += seg[j * kSumCols];
+    for (int j = 0; j < 4; ++j) a[j] += seg[j * kCols];
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) cols[c * 4 + j] = a[j];
@@ -521,81 +514,36 @@ struct SumArgs {
   double *rows, *cols;
 };
 
-// blocks of an instantiation that fit a CU at once (registers and LDS, from the runtime)
-template <int KS, int KT>
-int summary_blocks_per_cu() {
-  static const int nb = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, summary_kernel<KS, KT>, kSumThreads,
-                                                     0) != hipSuccess || n < 1)
-      n = sum_occ<KS, KT>();
-    return n;
-  }();
-  return nb;
-}
-
-template <int KS, int KT>
-hipError_t launch_summary(const SumArgs& a) {
-  const long long units = (long long)gp_ceil_div(a.ncols, kSumCols) * a.m;
-  const int nts = (a.S + sum_rows<KS>() - 1) / sum_rows<KS>();
-  // one residency round: no tail round of blocks
-  long long blocks = (long long)gp_num_cus() * summary_blocks_per_cu<KS, KT>();
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL((summary_kernel<KS, KT>), dim3((unsigned)blocks), dim3(kSumThreads), 0,
-                     a.stream, a.W, a.ldw, a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu,
-                     a.err, a.tlo, a.thi, a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts);
-  return hipGetLastError();
-}
-
-template <int KS, int KT>
-int score_blocks_per_cu() {
-  static const int nb = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, score_kernel<KS, KT>, kSumThreads,
-                                                     0) != hipSuccess || n < 1)
-      n = sum_occ<KS, KT>();
-    return n;
-  }();
-  return nb;
-}
-
 // blocks of the score launch: one residency round as the summary's, and never more than the
 // workspace has segments for
 constexpr long long kScoreMaxBlocks = 2048;
 
-template <int KS, int KT>
-hipError_t launch_score(const SumArgs& a) {
-  const long long npanels = gp_ceil_div(a.ncols, kSumCols), units = npanels * a.m;
-  const int nts = (a.S + sum_rows<KS>() - 1) / sum_rows<KS>();
-  long long blocks = (long long)gp_num_cus() * score_blocks_per_cu<KS, KT>();
-  if (blocks > kScoreMaxBlocks) blocks = kScoreMaxBlocks;
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL((score_kernel<KS, KT>), dim3((unsigned)blocks), dim3(kSumThreads), 0,
-                     a.stream, a.W, a.ldw, a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu,
-                     a.err, a.tlo, a.thi, a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts, a.sc);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const unsigned rblocks = (unsigned)a.m + (a.cols ? (unsigned)gp_ceil_div(a.ncols, 256) : 0u);
-  hipLaunchKernelGGL(score_reduce_kernel, dim3(rblocks), dim3(256), 0, a.stream, a.sc.rowp,
-                     a.sc.colp, a.m, a.ncols, npanels, blocks, a.rows, a.cols);
-  return hipGetLastError();
-}
-
-template <int KT, bool SCORE>
-hipError_t dispatch_summary_ks(const SumArgs& a) {
-  const int ks = (a.P + 3) / 4;
-  if constexpr (SCORE) {
-    if (ks <= 2) return launch_score<2, KT>(a);
-    if (ks <= 4) return launch_score<4, KT>(a);
-    if (ks <= 8) return launch_score<8, KT>(a);
-    if (ks <= 12) return launch_score<12, KT>(a);
-    return launch_score<16, KT>(a);
+// the summary (SCORE = false) or the score kernel and its reduction, on the grid of one residency
+// round of that instantiation
+template <int KS, int KT, bool SCORE>
+hipError_t launch_summary(const SumArgs& a) {
+  const long long npanels = gp_ceil_div(a.ncols, kCols), units = npanels * a.m;
+  const int nts = (a.S + tile_rows<KS>() - 1) / tile_rows<KS>();
+  if constexpr (!SCORE) {
+    constexpr auto kernel = summary_kernel<KS, KT>;
+    const long long blocks = round_blocks(blocks_per_cu<kernel>(sum_occ<KS, KT>()), units);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kThreads), 0, a.stream, a.W, a.ldw,
+                       a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu, a.err, a.tlo, a.thi,
+                       a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts);
+    return hipGetLastError();
   } else {
-    if (ks <= 2) return launch_summary<2, KT>(a);
-    if (ks <= 4) return launch_summary<4, KT>(a);
-    if (ks <= 8) return launch_summary<8, KT>(a);
-    if (ks <= 12) return launch_summary<12, KT>(a);
-    return launch_summary<16, KT>(a);
+    constexpr auto kernel = score_kernel<KS, KT>;
+    long long blocks = round_blocks(blocks_per_cu<kernel>(sum_occ<KS, KT>()), units);
+    if (blocks > kScoreMaxBlocks) blocks = kScoreMaxBlocks;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kThreads), 0, a.stream, a.W, a.ldw,
+                       a.lds, a.S, a.m, a.P, a.K, a.ldk, a.ncols, a.sd, a.mu, a.err, a.tlo, a.thi,
+                       a.mean, a.lo, a.hi, a.ldo, a.out_f32, nts, a.sc);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const unsigned rblocks = (unsigned)a.m + (a.cols ? (unsigned)gp_ceil_div(a.ncols, 256) : 0u);
+    hipLaunchKernelGGL(score_reduce_kernel, dim3(rblocks), dim3(256), 0, a.stream, a.sc.rowp,
+                       a.sc.colp, a.m, a.ncols, npanels, blocks, a.rows, a.cols);
+    return hipGetLastError();
   }
 }
 
@@ -617,7 +565,7 @@ int summary_check(const double* W, long long ldw, long long lds, int S, int m, i
   if (lds < 1 || lds < (m > 0 ? m - 1 : 0) * ldw + P) return -3;
   if (S < 1) return -4;
   if (m < 0) return -5;
-  if (P < 1 || P > kSumMaxP) return -6;
+  if (P < 1 || P > kMaxP) return -6;
   if (!K) return -7;
   if (ldk < ncols || ldk < 1) return -8;
   if (ncols < 0) return -9;
@@ -641,20 +589,24 @@ int summary_check(const double* W, long long ldw, long long lds, int S, int m, i
   return 0;
 }
 
+// KT = the instantiated list depth 2 / 4 / 8 that holds `depth`
 template <bool SCORE>
 hipError_t dispatch_summary(const SumArgs& a, int depth) {
-  return depth <= 2   ? dispatch_summary_ks<2, SCORE>(a)
-         : depth <= 4 ? dispatch_summary_ks<4, SCORE>(a)
-                      : dispatch_summary_ks<8, SCORE>(a);
+  return dispatch_ks(a.P, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    return depth <= 2   ? launch_summary<KS, 2, SCORE>(a)
+           : depth <= 4 ? launch_summary<KS, 4, SCORE>(a)
+                        : launch_summary<KS, 8, SCORE>(a);
+  });
 }
 
 // workspace of gp_field_score: the row partials (8 doubles per unit), then the column segments
 long long score_ws_layout(long long m, long long ncols, long long* col_off) {
-  const long long npanels = (ncols + kSumCols - 1) / kSumCols, units = npanels * m;
+  const long long npanels = (ncols + kCols - 1) / kCols, units = npanels * m;
   const long long nb = units < kScoreMaxBlocks ? units : kScoreMaxBlocks;
   const long long rows_b = align256(units * 8 * (long long)sizeof(double));
   if (col_off) *col_off = rows_b;
-  return rows_b + align256((npanels + nb - 1) * 4 * kSumCols * (long long)sizeof(double));
+  return rows_b + align256((npanels + nb - 1) * 4 * kCols * (long long)sizeof(double));
 }
 
 }  // namespace

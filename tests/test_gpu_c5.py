@@ -41,7 +41,7 @@ def _generic(w2, K, sd, mu, e, f32):
     return y.to(torch.float32) if f32 else y.contiguous()
 
 
-@pytest.mark.parametrize("P", [1, 7, 25, 33, 64])
+@pytest.mark.parametrize("P", [1, 7, 12, 25, 33, 64])       # k-steps 2, 2, 4, 8, 12, 16
 @pytest.mark.parametrize("rows,ncols", [(1, 1), (37, 300), (1000, 513), (4099, 1000)])
 def test_field_kernel_equals_generic_path(dev, P, rows, ncols):
     from gladsgp_amd import blas

@@ -139,6 +139,26 @@ def test_sample_order(dev, P, order):
         _check(got, _reference(W3, K, sd, mu, e, q), S, exact_extremes=(q == (0, 1)))
 
 
+@pytest.mark.parametrize("P", [5, 12, 25, 40, 64])       # k-steps 2, 4, 8, 12, 16
+def test_one_sample_is_the_field(dev, P):
+    """S = 1, q = (0, 1): the lists hold the one value, _lerp at t = 0 returns it and the mean is
+    y + 0 over 1, so the summary's maps are gp_field's elements themselves: mean = field without
+    the error term, lo = hi = field with it, bit for bit, fp64 and float32 (three panels, the
+    last one ragged; strided W and K)."""
+    from gladsgp_amd import blas
+    m, ncols = 37, 300
+    W3, K, sd, mu, e = _inputs(dev, 1, m, P, ncols, True, True, seed=P)
+    assert W3.stride(1) > P and K.stride(0) > ncols
+    for f32 in (False, True):
+        mean, lo, hi = blas.field_summary(W3, K, sd, mu, e, q=(0, 1), f32=f32)
+        y = blas.field(W3[0], K, sd, mu, None, f32=f32)
+        z = blas.field(W3[0], K, sd, mu, e, f32=f32)
+        assert mean.dtype == y.dtype and mean.shape == y.shape == (m, ncols)
+        assert torch.equal(mean, y), f32
+        assert torch.equal(lo, z), f32
+        assert torch.equal(hi, z), f32
+
+
 @pytest.mark.parametrize("f32", [True, False])
 def test_output_views_any_alignment(dev, f32):
     """Outputs written into a column block of a wider buffer at element offsets 0-3: the block
