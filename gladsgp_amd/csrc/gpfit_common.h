@@ -108,7 +108,13 @@ GP_DEV double fma_sc(double p, double r, double c) {
   return o;
 }
 
-GP_DEV double exp_neg(double a) {
+// exp_neg_scaled(a, s) = s exp(-a) with the scale applied to the polynomial's value before the
+// ldexp, so a result below the normal range is rounded once (s (ldexp(p, k)) rounds exp(-a)
+// into the subnormal grid first and then magnifies that error by s: 2^-33 relative at s = 2^20).
+// Where the result is normal the two forms give the same bits (ldexp is exact there).  "Once"
+// holds while s p is itself a normal number, 2^-1021 <= |s| < 2^1023 (p in [0.70, 1.42]): a
+// smaller s rounds s p into the subnormal grid before the ldexp, a larger one overflows.
+GP_DEV double exp_neg_scaled(double a, double s) {
   const double x = -fmin(a, 1100.0);
   const double k = __builtin_rint(x * 0x1.71547652b82fep+0);              // x log2(e)
   double r = fma(k, -0x1.62e42fefa39efp-1, x);                             // - k ln2 (hi)
@@ -124,8 +130,10 @@ GP_DEV double exp_neg(double a) {
   p = fma_sc(p, r, 0x1.000000000000bp-1);
   p = fma(p, r, 1.0);
   p = fma(p, r, 1.0);
-  return fma(a, 0.0, __builtin_ldexp(p, (int)k));
+  return fma(a, 0.0, __builtin_ldexp(p * s, (int)k));
 }
+
+GP_DEV double exp_neg(double a) { return exp_neg_scaled(a, 1.0); }
 
 // exp(-a) from a 64-entry table (the prediction's cross-covariance, predict.hip): with
 // q = rint(-a 64 / ln2), exp(-a) = 2^(q >> 6) T[q & 63] exp(r), T[j] = 2^(j / 64) correctly
@@ -135,6 +143,8 @@ GP_DEV double exp_neg(double a) {
 // 12 fp64 operations instead of exp_neg's 17 -- the cross-covariance of a batch is bound by its
 // fp64 VALU work (C4 chunk 596 -> 472 us, profiles/r05/r05e_cross_micro.log).  `tab` is an
 // LDS copy of kExp2Tab (per-lane indices).  NaN / Inf arguments propagate as in exp_neg.
+// The one form is exp_neg_tab_scaled(a, s, tab) = s exp(-a), scaled before the ldexp as
+// exp_neg_scaled is (both callers scale; an unscaled wrapper would have no user).
 static __constant__ double kExp2Tab[64] = {
     0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,
     0x1.0b5586cf9890fp+0, 0x1.0e3ec32d3d1a2p+0, 0x1.11301d0125b51p+0, 0x1.1429aaea92de0p+0,
@@ -154,7 +164,7 @@ static __constant__ double kExp2Tab[64] = {
     0x1.ea4afa2a490dap+0, 0x1.efa1bee615a27p+0, 0x1.f50765b6e4540p+0, 0x1.fa7c1819e90d8p+0,
 };
 
-GP_DEV double exp_neg_tab(double a, const double* tab) {
+GP_DEV double exp_neg_tab_scaled(double a, double s, const double* tab) {
   const double x = -fmin(a, 1100.0);
   const double q = __builtin_rint(x * 0x1.71547652b82fep+6);               // x 64 / ln2
   double r = fma(q, -0x1.62e42fefa39efp-7, x);                             // - q ln2/64 (hi)
@@ -166,7 +176,7 @@ GP_DEV double exp_neg_tab(double a, const double* tab) {
   p = p * r;                                                               // exp(r) - 1
   const int qi = (int)q;
   const double t = tab[qi & 63];
-  return fma(a, 0.0, __builtin_ldexp(fma(t, p, t), qi >> 6));
+  return fma(a, 0.0, __builtin_ldexp(fma(t, p, t) * s, qi >> 6));
 }
 
 // Squared ARD distance sum_k beta_k (a_k - b_k)^2 ; D is a compile-time dimension bound.

@@ -17,7 +17,8 @@
 // registers and the staged d-tile, once per problem / segment): sum_k (a'_k - b'_k)^2 with
 // a' = sqrt(beta) a costs 2 d ops per element instead of 3 d (beta >= 0, the ARD precisions);
 // the rounding of the scaled values adds at most ~2 eps s to an element (|x| <= 1, beta <= 5),
-// inside the 8 eps s Gram tolerance.
+// inside the 8 eps s Gram tolerance; in general it grows with sqrt(beta) |x| (the bound is in
+// include/gpfit.h, "accuracy of a kernel value").
 // Roofline: 8 B written per output element + 8 d B read per row/column vector (amortised),
 // and per element ~37 fp64 VALU ops (2 d for the distance, 19 for exp_neg, the store
 // address).  At n = 4096 (lower triangle, 133k column units of 64 elements) the stores
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void ardse_kernel(
           const double dt = xa[k] - xb[k];
           acc = fma(dt, dt, acc);
         }
-        o[(long long)(j0 + c) * ldo] = sb * exp_neg(acc);
+        o[(long long)(j0 + c) * ldo] = exp_neg_scaled(acc, sb);
       }
     } else {
       const bool row_ok = i < na, row_st = i < rows_out;
@@ -149,7 +150,8 @@ __global__ __launch_bounds__(256) void ardse_kernel(
           const double dt = xa[k] - xb[k];
           acc = fma(dt, dt, acc);
         }
-        double v = fma(sb, exp_neg(acc), (i == j) ? db : 0.0);
+        double v = exp_neg_scaled(acc, sb);
+        if (i == j) v += db;                             // acc = 0: fl(s + delta), one rounding
         v = (row_ok && j < nb) ? v : 0.0;
         if (row_st && (!g.lower || j <= i)) o[(long long)j * ldo] = v;
       }

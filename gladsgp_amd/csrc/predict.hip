@@ -37,7 +37,7 @@ constexpr int kDefaultChunkSingle = 16384;            // ... and for one GP
 
 // Cross-covariance chunk, k-major as the TRMM streams it:
 //   Kt[k * mc + c] = s * exp(-sum beta (X[k] - Xs[c])^2)
-// (exp by the 64-entry table, exp_neg_tab: the kernel is bound by its fp64 VALU work)
+// (exp by the 64-entry table, exp_neg_tab_scaled: the kernel is bound by its fp64 VALU work)
 // (zero for k >= n or c >= mv).  Each thread owns one test point c (registers) and walks 32
 // k-pairs whose design rows are broadcast from LDS; a wave stores 512 contiguous bytes per
 // row k.  Both design vectors are pre-scaled by sqrt(beta) (beta >= 0): 2 d ops per element
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void cross_kp_kernel(
     }
     // exp unconditionally, then select: padding rows / columns have finite (zeroed) inputs,
     // and a conditional exp costs an exec-mask branch around each call
-    const double v0 = sb * exp_neg_tab(e0, tab), v1 = sb * exp_neg_tab(e1, tab);
+    const double v0 = exp_neg_tab_scaled(e0, sb, tab), v1 = exp_neg_tab_scaled(e1, sb, tab);
     // non-temporal stores (the chunk, 2.15 GB at C4, is read back by the TRMM from HBM either
     // way): C4 59.1-59.6 -> 58.7-58.8 ms per step, C3 unchanged
     // (profiles/r06/r06ai_ab_cross_nt.log)
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(64 * kResWaves, kResOcc) void trmm_res_kernel(const
       const double t = xk[dd] - xc[dd * kResCols];
       e = fma(t, t, e);
     }
-    const double v = sb * exp_neg_tab(e, tab);
+    const double v = exp_neg_tab_scaled(e, sb, tab);
     *bslot(c, h) = (col_ok && k < a.n) ? v : 0.0;
   };
   auto produce = [&](int c, int slot) {

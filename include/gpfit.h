@@ -19,6 +19,32 @@
  *    A[i + j*ld]; design matrices X (n x d) are row-major with row stride ldx >= d;
  *  - beta holds ARD precisions, beta >= 0 (the kernels take sqrt(beta); a negative entry
  *    yields NaN, which the factorisation reports through info);
+ *  - accuracy of a kernel value k = s exp(-sum_k beta_k (a_k - b_k)^2) (gp_gram_ardse,
+ *    gp_cross_ardse, the prediction's cross-covariance).  The coordinates are scaled by
+ *    q_k = sqrt(beta_k) before they are subtracted, so the rounding of q_k a_k and q_k b_k enters
+ *    with the size of the coordinates, not of their difference.  With t_k = q_k (a_k - b_k),
+ *    acc = sum_k t_k^2 and eps = 2^-52, relative to the exact value
+ *      |dk| / k <= eps ( sum_k |t_k| q_k (|a_k| + |b_k|) + (2 + d/2) acc + 2 ),
+ *    plus 2^-1074 absolute where k is below the normal range.  That last figure holds for
+ *    2^-1021 <= |s| < 2^1023: the scale is applied before the result is rounded into the
+ *    subnormal range, which needs 1.42 s finite and 0.70 s normal; with a smaller s such a
+ *    result is rounded twice, a larger s overflows.  On the unit cube with beta <= 5 the bound
+ *    is a few eps; it grows like sqrt(beta) |x| sqrt(acc), e.g. 2e-11 at |x| = 64, beta = 800,
+ *    acc = 700.  A value whose exact size is below 2^-1075 is +0; acc is clamped at 1100.
+ *    tests/test_gpu_extremes.py holds the three kernels to twice this bound over acc = 0 ... 1200;
+ *  - accuracy of the factorisation and what is built on it.  No entry point back-substitutes:
+ *    the factorisation inverts every diagonal block and multiplies (L_ik = A_ik D_k^T with
+ *    D_k = L_kk^-1, on 64 x 64 blocks and, in the persistent kernel, on 16 x 16 blocks inside
+ *    them), and z, alpha, the predictive mean and variance are products with the explicit L^-1.
+ *    A product with a computed inverse is not backward stable: its error is that of a
+ *    substitution times cond(L_kk).  Where the diagonal blocks are well conditioned -- every
+ *    regime of the sampler on a scattered design -- the results are within a small multiple of
+ *    what LAPACK's potrf / trsm give (measured: at most 7x their spread over orderings).  On
+ *    blocks that are themselves near-singular (a smooth kernel on a fine 1-D grid with a jitter
+ *    of 1e-7: cond(A) = 5e8, cond(L_kk) ~ 1e4) L, L^-1, z, alpha, mean and var are 30 ... 600
+ *    times further from the exact values than LAPACK's, e.g. mean to 4e-11 instead of 1e-13 of
+ *    its scale; info stays 0 and the results stay finite.  DESIGN.md §7 has the measured table;
+ *    tests/_mp_ref.py (explicit_inverse_term) restates the arithmetic and derives the term;
  *  - `batch` independent problems share X / Xs; per-problem operands advance by the given
  *    stride (matrices), by ldbeta (beta rows), by 1 (s, delta, s_pred, info, logdet) and by
  *    ldw / ldo (w_hat, mean, var columns);
