@@ -15,7 +15,7 @@
 
 namespace {
 
-constexpr int kMaxR = 1024;   // LDS: rotations + pairing + sort keys, ~30 KB
+constexpr int kMaxR = 1024;   // LDS: rotations + pivot diagonals + pairing + sort keys, ~38 KB
 // r <= kLdsR: A and V live in LDS for the whole solve (2 x 64 x 65 doubles): a global round
 // trip per phase (3 per round, 63 rounds per sweep at r = 64) made the L2-resident form take
 // 3.35 ms for the C5 basis's 64 x 64 B B^T (profiles/r06/r06b_c5_kernel_stats.csv)
@@ -41,7 +41,7 @@ struct LMat {
 // with V's column rotations beside them: two barriers per round instead of three.
 template <bool FUSE, typename MA, typename MV>
 GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs, double* sn,
-                       int* pp, int* qq, double* red, int* done) {
+                       double* dp, double* dq, int* pp, int* qq, double* red, int* done) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int R = (r + 1) & ~1;          // padded to even; index r (if any) is a dummy
   const int npair = R / 2;
@@ -49,14 +49,34 @@ GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs
     const int i = g % r, j = g / r;
     V(i, j) = (i == j) ? 1.0 : 0.0;
   }
+  // The stop rule compares sums of squares, which leave the fp64 range long before the entries
+  // do (2^-600 squares to 0, 2^520 to inf: "0 <= 0" or "inf <= inf", converged at sweep 0).
+  // One power of two from max|a| of the input normalises them: Jacobi rotations preserve
+  // ||A||_F, so the scaled entries stay below 2r in every sweep, and where the squares were in
+  // range the scaling is exact and decides nothing differently.
+  double amax = 0.0;
+  for (int g = tid; g < r * r; g += nt) amax = fmax(amax, fabs(A(g % r, g / r)));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = amax;
+  __syncthreads();
+  if (tid == 0) {
+    double m = 0.0;
+    for (int q = 0; q < (nt + 63) / 64; ++q) m = fmax(m, red[q]);
+    int e = (m > 0.0 && m <= 1.7976931348623157e308) ? ilogb(m) : 0;
+    e = e < -1022 ? -1022 : e;         // 2^-e stays finite for a subnormal maximum
+    red[16] = scalbn(1.0, -e);
+  }
+  __syncthreads();
+  const double nrm = red[16];
   __syncthreads();
   int sweep = 0;
   for (; sweep < max_sweeps; ++sweep) {
-    // convergence check: off-diagonal vs total Frobenius norm
+    // convergence check: off-diagonal vs total Frobenius norm (of the normalised entries)
     double off = 0.0, tot = 0.0;
     for (int g = tid; g < r * r; g += nt) {
       const int i = g % r, j = g / r;
-      const double a = A(i, j);
+      const double a = A(i, j) * nrm;
       tot += a * a;
       if (i != j) off += a * a;
     }
@@ -91,7 +111,7 @@ GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs
         auto idx = [&](int pos) { return pos == 0 ? 0 : 1 + (pos - 1 + round) % (R - 1); };
         int p = idx(a), q = idx(b);
         if (p > q) { const int t = p; p = q; q = t; }
-        double c = 1.0, s = 0.0;
+        double c = 1.0, s = 0.0, dpp = 0.0, dqq = 0.0;
         if (q < r) {
           const double apq = A(p, q);
           if (apq != 0.0) {
@@ -100,10 +120,18 @@ GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs
             const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
             c = 1.0 / sqrt(1.0 + t * t);
             s = t * c;
+            // the pivot block in closed form (Rutishauser): a_pq = 0 exactly and the diagonal
+            // moves by t a_pq, one rounding each instead of the eight products of J^T A J --
+            // the diagonal's rounding, summed over r - 1 rotations a sweep, is the
+            // eigenvalues' error
+            dpp = app - t * apq;
+            dqq = aqq + t * apq;
           }
         }
         cs[tid] = c;
         sn[tid] = s;
+        dp[tid] = dpp;
+        dq[tid] = dqq;
         pp[tid] = p;
         qq[tid] = q;
       }
@@ -126,11 +154,15 @@ GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs
           }
           if (cq) {
             const double c = cs[u], s = sn[u];
-            A(p, pu) = c * xp0 - s * xp1;
-            A(p, qu) = s * xp0 + c * xp1;
+            // (the pair's own block when t == u; its closed form is read unconditionally so the
+            // four results are selects, not divergent branches)
+            const double dpt = dp[u], dqt = dq[u];
+            const bool pivot = t == u && s != 0.0;
+            A(p, pu) = pivot ? dpt : c * xp0 - s * xp1;
+            A(p, qu) = pivot ? 0.0 : s * xp0 + c * xp1;
             if (rq) {
-              A(q, pu) = c * xq0 - s * xq1;
-              A(q, qu) = s * xq0 + c * xq1;
+              A(q, pu) = pivot ? 0.0 : c * xq0 - s * xq1;
+              A(q, qu) = pivot ? dqt : s * xq0 + c * xq1;
             }
           } else {
             A(p, pu) = xp0;
@@ -167,8 +199,12 @@ GP_DEV int syevj_solve(MA A, MV V, int r, int max_sweeps, double tol, double* cs
         if (q >= r) continue;
         const double c = cs[t], s = sn[t];
         double x = A(k, p), y = A(k, q);
-        A(k, p) = c * x - s * y;
-        A(k, q) = s * x + c * y;
+        // the pivot block, as in the fused form (selects on values read unconditionally)
+        const double dpt = k == p ? dp[t] : 0.0, dqt = k == q ? dq[t] : 0.0;
+        const bool pivot = s != 0.0 && (k == p || k == q);
+        const double ap = c * x - s * y, aq = s * x + c * y;
+        A(k, p) = pivot ? dpt : ap;
+        A(k, q) = pivot ? dqt : aq;
         x = V(k, p);
         y = V(k, q);
         V(k, p) = c * x - s * y;
@@ -221,14 +257,15 @@ __global__ __launch_bounds__(1024) void syevj_kernel(double* __restrict__ A, int
                                                      int max_sweeps, double tol,
                                                      int* __restrict__ sweeps_out,
                                                      int want_sqrt) {
-  __shared__ double cs[kMaxR / 2], sn[kMaxR / 2];
+  __shared__ double cs[kMaxR / 2], sn[kMaxR / 2], dp[kMaxR / 2], dq[kMaxR / 2];
   __shared__ int pp[kMaxR / 2], qq[kMaxR / 2];
   __shared__ double red[17];
   __shared__ int perm[kMaxR];
   __shared__ double ws[kMaxR];
   __shared__ int done;
   const GMat Ag{A, lda}, Vg{V, ldv};
-  const int sweep = syevj_solve<false>(Ag, Vg, r, max_sweeps, tol, cs, sn, pp, qq, red, &done);
+  const int sweep = syevj_solve<false>(Ag, Vg, r, max_sweeps, tol, cs, sn, dp, dq, pp, qq,
+                                       red, &done);
   syevj_finish(Ag, Vg, r, sweep, W, Vg, perm, ws, sweeps_out, want_sqrt);
 }
 
@@ -241,7 +278,7 @@ __global__ __launch_bounds__(1024) void syevj_lds_kernel(double* __restrict__ A,
                                                          int* __restrict__ sweeps_out,
                                                          int want_sqrt) {
   __shared__ double al[kLdsR * kLdsPitch], vl[kLdsR * kLdsPitch];
-  __shared__ double cs[kLdsR / 2], sn[kLdsR / 2];
+  __shared__ double cs[kLdsR / 2], sn[kLdsR / 2], dp[kLdsR / 2], dq[kLdsR / 2];
   __shared__ int pp[kLdsR / 2], qq[kLdsR / 2];
   __shared__ double red[17];
   __shared__ int perm[kLdsR];
@@ -254,7 +291,8 @@ __global__ __launch_bounds__(1024) void syevj_lds_kernel(double* __restrict__ A,
     Al(i, j) = A[i + (long long)j * lda];
   }
   __syncthreads();
-  const int sweep = syevj_solve<true>(Al, Vl, r, max_sweeps, tol, cs, sn, pp, qq, red, &done);
+  const int sweep = syevj_solve<true>(Al, Vl, r, max_sweeps, tol, cs, sn, dp, dq, pp, qq,
+                                       red, &done);
   syevj_finish(Al, Vl, r, sweep, W, GMat{V, ldv}, perm, ws, sweeps_out, want_sqrt);
   for (int g = tid; g < r * r; g += nt) {
     const int i = g % r, j = g / r;

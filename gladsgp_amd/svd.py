@@ -16,9 +16,11 @@ Build (all arithmetic in libgpfit, fp64):
     Cholesky + inverse is ``gp_potrf_inv``;
   * a rank-deficient ``Y`` (e.g. ``init_model``'s ``r = min(25, n, ny)`` on a column-centred
     ensemble of n <= 25 runs, rank <= n - 1) makes a CholeskyQR pass fail; numpy's Householder
-    QR still returns an orthonormal Q there.  The fallback: eigen-basis of ``Y^T Y``
-    (gp_syevj) for the numerically nonzero directions, CholeskyQR2 to restore orthogonality,
-    and a seeded orthonormal completion of the null directions (B = Q^T X sees only range(X)
+    QR still returns an orthonormal Q there; so does a ``Y`` too ill-conditioned for the
+    shift (``k = None`` on a decaying spectrum).  The fallback: eigen-basis of ``Y^T Y``
+    (gp_syevj) for the directions above 1e-5 ||Y||, CholeskyQR to restore orthogonality,
+    deflation, and the same again on what is left until only Y's own rounding remains;
+    then a seeded orthonormal completion of the null directions (B = Q^T X sees only range(X)
     there, so any completion gives the reference's U, S, Vh up to the zero singular values);
   * ``svd(B)`` comes from the Jacobi eigendecomposition of ``B B^T`` (``gp_syevj``, r <= 1024):
     ``S = sqrt(eig)``, ``V^T = S^-1 U_B^T B``.
@@ -81,33 +83,61 @@ def orthonormalize(Y: CM) -> CM:
         return _orthonormalize_deficient(Y)
 
 
+def _project_off(P: CM, Z: CM) -> CM:
+    """Z <- (I - P P^T) Z, twice (P orthonormal columns); in place."""
+    for _ in range(2):
+        C = gemm(True, False, P, Z)
+        gemm(False, False, P, C, alpha=-1.0, beta=1.0, C=Z)
+    return Z
+
+
 def _orthonormalize_deficient(Y: CM, rel_tol: float = 1e-10, seed: int = 0x5EED) -> CM:
+    """Rank-revealing basis of range(Y) in stages.  A stage takes the eigen-directions of R^T R
+    (R = Y at first) above rel_tol of its largest eigenvalue -- a factor 1e5 in singular value,
+    which CholeskyQR3 orthonormalises safely -- and deflates them from R; the next stage works on
+    what is left, at its own scale.  So directions of Y down to the rounding of Y itself
+    (8 sqrt(n r) u ||Y||) enter the basis, as they do in a Householder QR: one stage alone
+    dropped everything below 1e-5 ||Y||, and with it every singular value of X below
+    (1e-5)^(1/(2q+1)) S_0 once Y = (X X^T)^q X Omega is too ill-conditioned for CholeskyQR3
+    (k = None on a decaying spectrum).  What remains below the rounding is completed by seeded
+    Gaussian columns."""
     n, r = Y.rows, Y.cols
     dev = Y.t.device
-    G = gemm(True, False, Y, Y)                              # r x r = Y^T Y
-    lam, V, _ = syevj(G, want_sqrt=False)                    # descending
-    lam_h = lam.cpu().numpy()
-    k = int(np.sum(lam_h > rel_tol * max(lam_h[0], 0.0))) if r else 0
-    parts = []
-    if k:
-        Vk = CM(V.t[:k], r, k, V.ld)                         # first k eigenvectors
-        Q1 = gemm(False, False, Y, Vk)                       # n x k, cond <= rel_tol^-1/2
-        Q1 = _chol_qr(_chol_qr(_chol_qr(Q1, shift=True), shift=False), shift=False)
-        parts.append(Q1)
-    if k < r:
-        # seeded Gaussian columns, projected off range(Q1) twice, then CholeskyQR2
-        z = np.random.default_rng(seed).standard_normal((r - k, n))
-        Z = CM.of_rowmajor(torch.as_tensor(z, dtype=torch.float64, device=dev))  # n x (r-k)
-        if k:
-            for _ in range(2):
-                P = gemm(True, False, parts[0], Z)           # k x (r-k)
-                gemm(False, False, parts[0], P, alpha=-1.0, beta=1.0, C=Z)
-        parts.append(_chol_qr(_chol_qr(Z, shift=False), shift=False))
     Q = CM.empty(n, r, dev)
-    c = 0
-    for part in parts:
-        Q.t[c:c + part.cols, :n] = part.t[: part.cols, :n]
-        c += part.cols
+    found = 0
+    R, floor = Y, None
+    while found < r:
+        G = gemm(True, False, R, R)                          # r x r = R^T R
+        lam, V, _ = syevj(G, want_sqrt=False)                # descending
+        lam_h = lam.cpu().numpy()
+        top = float(lam_h[0])
+        if floor is None:
+            floor = 64.0 * n * r * _U * _U * max(top, 0.0)
+        if not top > floor:                                  # what is left is rounding (or 0)
+            break
+        k = min(int(np.sum(lam_h > max(rel_tol * top, floor))), r - found)
+        Vk = CM(V.t[:k], r, k, V.ld)                         # first k eigenvectors
+        Q1 = gemm(False, False, R, Vk)                       # n x k, cond <= rel_tol^-1/2
+        Q1 = _chol_qr(_chol_qr(_chol_qr(Q1, shift=True), shift=False), shift=False)
+        if found:
+            # R was deflated at the previous stages' scale: relative to this one's the basis
+            # found so far still shows, so project it off the unit vectors and renormalise
+            Q1 = _project_off(CM(Q.t[:found], n, found, Q.ld), Q1)
+            Q1 = _chol_qr(_chol_qr(Q1, shift=False), shift=False)
+        Q.t[found:found + k, :n] = Q1.t[:k, :n]
+        found += k
+        if found < r:
+            if R is Y:
+                R = CM(Y.t.clone(), n, r, Y.ld)
+            _project_off(Q1, R)
+    if found < r:
+        # seeded Gaussian columns, projected off the basis found twice, then CholeskyQR2
+        z = np.random.default_rng(seed).standard_normal((r - found, n))
+        Z = CM.of_rowmajor(torch.as_tensor(z, dtype=torch.float64, device=dev))  # n x (r-found)
+        if found:
+            _project_off(CM(Q.t[:found], n, found, Q.ld), Z)
+        Z = _chol_qr(_chol_qr(Z, shift=False), shift=False)
+        Q.t[found:r, :n] = Z.t[: r - found, :n]
     return Q
 
 

@@ -463,7 +463,8 @@ int gp_gemm_ex(int transa, int transb, int m, int n, int k, double alpha,
                double beta, double* C, int ldc, void* ws, long long ws_bytes, hipStream_t stream);
 
 /* Per-location statistics over simulations of a C-order ensemble Y (n x ny, row stride ldy):
- * mu = mean over rows, sd = std(ddof=1) floored at sd_floor — src/model.py:60-64. */
+ * mu = mean over rows, sd = std(ddof=1) floored at sd_floor — src/model.py:60-64.  n = 1 has no
+ * sample deviation (numpy's ddof = 1 gives NaN there): sd is then the floor, mu the row itself. */
 int gp_sim_stats(const double* Y, int n, int ny, long long ldy, double sd_floor,
                  double* mu, double* sd, hipStream_t stream);
 
@@ -740,7 +741,10 @@ int gp_rowscale(double* M, int rows, int cols, int ld, const double* f, int inv,
 /* Symmetric eigendecomposition A = V diag(W) V^T by cyclic Jacobi (r <= 1024, one workgroup),
  * eigenvalues descending (want_sqrt = 1: W = sqrt(max(eig, 0)), the singular values when
  * A = B B^T); A is destroyed.  `sweeps` (device int, may be NULL) receives the sweep count.
- * The r x r core of np.linalg.svd(B) in src/svd.py:63 (via B B^T). */
+ * The r x r core of np.linalg.svd(B) in src/svd.py:63 (via B B^T).  Sweeps stop at
+ * off(A) <= tol ||A||_F, measured on entries normalised by a power of two taken from max|a| of
+ * the input: A 2^k gives W 2^k, the same V and the same sweep count bit for bit wherever the
+ * entries and the rotations' products stay in the normal range (no absolute threshold). */
 int gp_syevj(double* A, int r, int lda, double* W, double* V, int ldv, int max_sweeps,
              double tol, int* sweeps, int want_sqrt, hipStream_t stream);
 

@@ -1,9 +1,11 @@
-"""Print DESIGN.md section 7's table: the measured error / noise of every chain quantity per
+"""Print DESIGN.md section 7's tables: the measured error / noise of every chain quantity per
 (regime, n), worst over the entry points that produce it and over the factorisation paths, from
-the helpers of tests/test_gpu_extremes.py.  Needs a HIP device.  Entries above 16 also show, in
-parentheses, error / (noise + explicit-inverse term): they must be in tests/_mp_ref.FINDINGS.
+the helpers of tests/test_gpu_extremes.py; then the same for the PCA front end (statistics,
+eigensolver, randomized SVD, weights) from tests/test_gpu_pca_extremes.py.  Needs a HIP device.
+Entries above 16 also show, in parentheses, 16 error / bound with the documented term: they must
+be in tests/_mp_ref.FINDINGS or tests/_mp_pca_ref.FINDINGS.
 
-    python tools/extremes_ratios.py
+    python tools/extremes_ratios.py [chain|pca]
 """
 import os
 import sys
@@ -13,17 +15,19 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import torch  # noqa: E402
 
+import numpy as np  # noqa: E402
+
+import _mp_pca_ref as P  # noqa: E402
 import _mp_ref as M  # noqa: E402
 import test_gpu_extremes as T  # noqa: E402
+import test_gpu_pca_extremes as TP  # noqa: E402
 
 
 def fmt(x):
     return f"{x:.2g}" if x < 100 else f"{round(x)}"
 
 
-def main():
-    from gladsgp_amd import kernels  # noqa: F401 (loads libgpfit.so)
-    dev = torch.device("cuda:0")
+def chain(dev):
     sources = dict(T.SOURCES, mean=["mean/" + s for s in T.PRED_SOURCES],
                    var=["var/" + s for s in T.PRED_SOURCES])
     print("| regime | n | " + " | ".join(sources) + " |")
@@ -41,6 +45,62 @@ def main():
                         cell += " NOT A DOCUMENTED FINDING"
                 cells.append(cell)
             print(f"| {regime} | {n} | " + " | ".join(cells) + " |")
+
+
+def _worst(err, nz):
+    err, nz = np.asarray(err, dtype=float), np.asarray(nz, dtype=float)
+    with np.errstate(all="ignore"):
+        ratio = np.where(nz > 0, err / nz, np.where(err > 0, np.inf, 0.0))
+    return float(np.max(ratio)) if ratio.size else 0.0
+
+
+def pca(dev):
+    print("\n| statistics (n, ny) | mu | sd | y_std |")
+    print("|---|---|---|---|")
+    for n, ny in TP.STAT_SHAPES:
+        err, _ = TP.stats_errors(dev, n, ny)
+        print(f"| {n}, {ny} | " + " | ".join(fmt(_worst(*err[q])) for q in ("mu", "sd", "y_std"))
+              + " |")
+    print("\n| gp_syevj input | r | W | V^T V - I | A V - V W |")
+    print("|---|---|---|---|---|")
+    for kind in P.EIG_KINDS:
+        for r in TP.EIG_SIZES:
+            e = TP.eig_errors(dev, kind, r)
+            print(f"| {kind} | {r} | " + " | ".join(fmt(_worst(*e[q])) for q in ("W", "VtV", "AV"))
+                  + " |")
+    cols = ("S", "U", "Vh", "PU0", "PV0", "UtU", "VVt", "resid")
+    print("\n| randomized_svd case | " + " | ".join(cols) + " |")
+    print("|---|" + "---|" * len(cols))
+    for case in P.SVD_CASES:
+        e = TP.svd_errors(dev, case)
+        cells = []
+        for q in cols:
+            if q not in e:
+                cells.append("-")
+                continue
+            err, nz, lim = e[q]
+            cell = fmt(_worst(err, nz))
+            if np.any(np.asarray(err) > P.MARGIN * np.asarray(nz)):
+                cell += f" ({fmt(P.MARGIN * _worst(err, lim))})"
+                if (q, case) not in P.FINDINGS:
+                    cell += " NOT A DOCUMENTED FINDING"
+            cells.append(cell)
+        print(f"| {case} | " + " | ".join(cells) + " |")
+    print("\n| weights regime | w_hat | LamSim |")
+    print("|---|---|---|")
+    for regime in ("d2", "d4", "d6"):
+        e = TP.weights_errors(dev, regime)
+        print(f"| {regime} | {fmt(_worst(*e['w_hat']))} | {fmt(_worst(*e['LamSim']))} |")
+
+
+def main():
+    from gladsgp_amd import kernels  # noqa: F401 (loads libgpfit.so)
+    dev = torch.device("cuda:0")
+    which = sys.argv[1] if len(sys.argv) > 1 else "both"
+    if which in ("chain", "both"):
+        chain(dev)
+    if which in ("pca", "both"):
+        pca(dev)
 
 
 if __name__ == "__main__":
