@@ -146,6 +146,13 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_ll,
                                  c_void_p]),
+    "gp_predict_cov_ws_bytes": (c_ll, [c_int, c_int, c_int]),
+    "gp_predict_cov": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_int, c_void_p, c_int, c_int,
+                               c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_ll, c_int, c_void_p, c_ll, c_void_p]),
+    "gp_mvn_draw": (c_int, [c_void_p, c_int, c_ll, c_int, c_void_p, c_int, c_int,
+                            ctypes.c_ulonglong, ctypes.c_ulonglong, c_ll, c_void_p, c_ll, c_int,
+                            c_void_p]),
     "gp_shift_diag": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
     "gp_rowscale": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gp_syevj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

@@ -56,3 +56,11 @@ int gpfit_potrf_loglik(double* G, int n, long long strideG, double* D, long long
                        int* info, double* logdet, double* ll, int* status, int* info_out,
                        void* ws, long long ws_bytes, hipStream_t stream,
                        GpfitPre pre = GpfitPre());
+
+// K* = s exp(-sum beta (X - Xs)^2) of `batch` problems in the k-major image the prediction's TRMM
+// streams (predict.hip cross_kp_kernel, the values gp_predict multiplies): Kt[b * sK + k * mc + c]
+// for k < gp_padded_n(n), c < mc, zero where k >= n or c >= m.  mc >= m, sK >= mc gp_padded_n(n),
+// batch <= 65535.
+hipError_t gpfit_cross_kp_launch(const double* X, int ldx, const double* Xs, int ldxs, int n, int m,
+                                 int d, const double* beta, int ldbeta, const double* s,
+                                 double* Kt, int mc, long long sK, int batch, hipStream_t stream);

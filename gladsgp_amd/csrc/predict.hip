@@ -1736,3 +1736,16 @@ extern "C" int gp_predict_chol(const double* L, int ldl, long long strideL, cons
                   ws_bytes - head, m_chunk, stream);
   return rc;
 }
+
+// cross_kp_kernel for other translation units (gpfit_internal.h): K* of `batch` problems in the
+// TRMM's k-major image, gp_padded_n(n) rows of mc columns per problem (problem stride sK), zero
+// for rows >= n and columns >= m.  batch <= 65535 (the grid's z extent).
+hipError_t gpfit_cross_kp_launch(const double* X, int ldx, const double* Xs, int ldxs, int n, int m,
+                                 int d, const double* beta, int ldbeta, const double* s,
+                                 double* Kt, int mc, long long sK, int batch, hipStream_t stream) {
+  auto kern = cross_kp_kernel<8>;
+  if (d > 8) kern = d <= 16 ? cross_kp_kernel<16> : cross_kp_kernel<32>;
+  hipLaunchKernelGGL(kern, dim3(gp_ceil_div(mc, 256), gp_padded_n(n) / 64, batch), dim3(256), 0,
+                     stream, X, n, ldx, Xs, m, ldxs, d, beta, ldbeta, s, Kt, mc, sK);
+  return hipGetLastError();
+}

@@ -6,7 +6,9 @@
 // returns the posterior mean by default; gp_realize turns (mean, var) into one marginal draw
 //   out[i] = mean[i] + sqrt(max(var[i], 0)) * z_i ,   z_i ~ N(0, 1)
 // so those quantiles keep their predictive spread.  (SEPIA draws jointly over the m_b points of
-// a call; at m = 100k only the marginal is tractable — DESIGN.md.)
+// a call; at m = 100k only the marginal is tractable.  The joint draw over a block of up to
+// 4096 points is gp_predict_cov + gp_potrf + gp_mvn_draw, jointcov.hip, which reads this same
+// normal stream — DESIGN.md §4.6f.)
 //
 // z_i: counter-based Philox4x32-10 (Salmon et al., SC'11) keyed by `seed`, counter
 // (i / 2, offset); the four 32-bit words make two 53-bit uniforms, Box-Muller gives z_{2j} =

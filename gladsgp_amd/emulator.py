@@ -20,13 +20,18 @@ each), with betaU (S, (d+1) P) reshaped C-order to (S, d+1, P), row 0 the dummy 
 ``pred_nugget`` selects whether 1/lamWs is part of the predictive prior variance (SEPIA's
 exact choice is not verifiable offline — SURVEY §8c — so it is a flag, default on).
 
-Differences from SEPIA, by design: by default ``.w`` is the posterior MEAN per (sample, PC)
-and ``.var`` the marginal variance (SEPIA returns one joint random draw over the m_b x m_b
-covariance of a call, which does not scale to m = 100k).  ``realize=True`` makes ``.w`` one
-marginal draw per (sample, point, PC) instead (gp_realize, Philox4x32-10 on the device, seeded
-by ``seed``), so the reference's quantile / coverage statistics over ``get_y()``
-(assess_all_models.py:489-500) keep the GP's predictive spread; ``.mean`` always holds the
-posterior mean.  ``.w`` is assignable, as the reference's callers do
+Differences from SEPIA: by default ``.w`` is the posterior MEAN per (sample, PC) and ``.var``
+the marginal variance (SEPIA returns one joint random draw over the m_b x m_b covariance of a
+call, which does not scale to m = 100k).  ``realize=True`` makes ``.w`` one marginal draw per
+(sample, point, PC) instead (gp_realize, Philox4x32-10 on the device, seeded by ``seed``), so the
+reference's quantile / coverage statistics over ``get_y()`` (assess_all_models.py:489-500) keep
+the GP's predictive spread.  ``realize="joint"`` is SEPIA's own form for the block sizes it is
+used at (m <= ``joint_max_points``): the full m x m predictive covariance of every (sample, PC)
+GP (gp_predict_cov) and joint draws from it (gp_potrf + gp_mvn_draw), with ``.cov()`` and
+``.linear_functional()`` for what needs the correlation between test points.  SEPIA draws
+through an SVD of the covariance, this package through its Cholesky factor plus a jitter: the
+draws agree in distribution, not number for number.  ``.mean`` always holds the posterior mean.
+``.w`` is assignable, as the reference's callers do
 (``preds.w = preds.w.astype(np.float32)``, time_predictions.py:78, assess_all_models.py:490,
 513): ``get_y()`` then reconstructs from the assigned values and returns that dtype.  All
 arithmetic runs in libgpfit (fp64); the (sample, PC) pairs are one batched Gram ->
@@ -345,16 +350,35 @@ class EmulatorPrediction:
     ``shard`` forces "units" or "points".  ``group`` caps the GPs per batched factorisation.
     ``fctx`` / ``workspace``: a caller-owned gp_fit_predict context (cross-covariance beside the
     factorisation) and prediction workspace, reused across calls.
+
+    ``realize="joint"`` (single device, m <= ``joint_max_points``): ``.w`` is draw 0 of ``nsamp``
+    joint draws over the m test points per (sample, PC); per group of units under
+    ``budget_bytes`` the chain is gram -> cholesky_inverse -> predict -> predict_cov -> gp_potrf
+    -> mvn_draw.  ``.mean`` / ``.var`` have the default mode's bits.  Unit u = s P + j draws from
+    its own slice of the normal stream, so the draws do not depend on ``group`` /
+    ``budget_bytes``.  ``joint_jitter`` (a multiple of s added to the covariance's diagonal)
+    defaults to 0 with ``pred_nugget`` and 1e-8 without; a non-positive pivot raises
+    :class:`kernels.JointNotPositiveDefinite`.  See :meth:`sample_w`, :meth:`cov`,
+    :meth:`linear_functional`.
     """
+
+    joint_max_points = 4096
 
     def __init__(self, model: EmulatorModel = None, samples: dict = None, t_pred=None,
                  pred_nugget: bool = True, ctx: gdist.Context | None = None,
-                 budget_bytes: int = 2 << 30, m_chunk: int = 0, realize: bool = False,
+                 budget_bytes: int = 2 << 30, m_chunk: int = 0, realize=False,
                  seed: int | None = None, group: int | None = None, shard: str | None = None,
                  fctx: kernels.FitPredictContext | None = None,
-                 workspace: kernels.PredictWorkspace | None = None):
+                 workspace: kernels.PredictWorkspace | None = None,
+                 joint_jitter: float | None = None, nsamp: int = 1):
         if model is None or samples is None or t_pred is None:
             raise ValueError("EmulatorPrediction needs model, samples and t_pred")
+        if isinstance(realize, str):
+            if realize != "joint":
+                raise ValueError(f"realize must be False, True or 'joint', got {realize!r}")
+            self._init_joint(model, samples, t_pred, pred_nugget, ctx, budget_bytes, seed, group,
+                             workspace, joint_jitter, nsamp)
+            return
         self.model = model
         dev = model.device
         X = model.data.sim_data.t_dev
@@ -403,7 +427,131 @@ class EmulatorPrediction:
                           assemble_points(ctx, mean_l, var_l, self.m) if self.shard == "points"
                           else assemble_units(ctx, mean_l, var_l, len(units)))
 
-    def _set_results(self, ctx, realize, seed, both) -> None:
+    # ------------------------------------------------------------------------ joint mode
+    def _init_joint(self, model, samples, t_pred, pred_nugget, ctx, budget_bytes, seed, group,
+                    workspace, joint_jitter, nsamp) -> None:
+        if ctx is not None:
+            raise ValueError("ctx: joint draws are not sharded over devices (pass None)")
+        self.model = model
+        dev = model.device
+        Xs = (t_pred.to(device=dev, dtype=F64) if torch.is_tensor(t_pred) else
+              torch.as_tensor(np.asarray(t_pred), dtype=F64, device=dev))
+        Xs = Xs.reshape(-1, model.d).contiguous()
+        m = Xs.shape[0]
+        if m > self.joint_max_points:
+            raise ValueError(
+                f"realize='joint': {m} test points exceed joint_max_points = "
+                f"{self.joint_max_points} (an m x m covariance per (sample, PC)); predict in "
+                "blocks, or use the marginal mode (realize=True)")
+        if int(nsamp) < 1:
+            raise ValueError("nsamp must be at least 1")
+        beta, s, delta, sp = gp_params(samples, _np(model.LamSim), model.d, model.P, pred_nugget)
+        S, P = s.shape
+        self.S, self.m, self.P = S, m, P
+        self.shard = "units"
+        self.lamWOs = np.asarray(samples["lamWOs"], dtype=np.float64).reshape(S)
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)  # noqa
+        self.joint_jitter = float((0.0 if pred_nugget else 1e-8) if joint_jitter is None
+                                  else joint_jitter)
+        w_hat = model.w_hat.transpose(0, 1).contiguous()       # (P, n)
+        n = model.n
+        npad = kernels.padded_n(n)
+        per = 8 * (n * n + npad * npad + m * m) + \
+            int(kernels._capi.lib().gp_predict_cov_ws_bytes(n, max(m, 1), 1))
+        g = max(1, int(budget_bytes // per))
+        if group is not None:
+            g = max(1, min(g, int(group)))
+        # units (s, j) in s-major order
+        self._joint = dict(
+            X=model.data.sim_data.t_dev, Xs=Xs, beta=t(beta.reshape(S * P, -1)),
+            s=t(s.reshape(-1)), delta=t(delta.reshape(-1)), sp=t(sp.reshape(-1)),
+            jit=t(s.reshape(-1) * self.joint_jitter), w=w_hat.repeat(S, 1), g=g,
+            ws=workspace if workspace is not None else kernels.PredictWorkspace())
+        U = S * P
+        mean = torch.empty((U, m), dtype=F64, device=dev)
+        var = torch.empty((U, m), dtype=F64, device=dev)
+        self._set_results(None, False, seed, (mean, var), fill=False)
+        self.realized = "joint"
+        self.nsamp = int(nsamp)
+        draws = self._joint_draws(self.seed, 0, self.nsamp, mean_out=(mean, var))
+        self.mean_dev = mean.reshape(S, P, m).permute(0, 2, 1).contiguous()
+        self.var_dev = var.reshape(S, P, m).permute(0, 2, 1).contiguous()
+        self.joint_w_dev = draws                               # (nsamp, S, m, P)
+        self.w_dev = draws[0]
+
+    def _joint_groups(self, mean_out=None):
+        """The chain of one group of units at a time: yields (a, b, mean (b - a, m), C
+        (b - a, m, m)), C in a buffer the caller may overwrite."""
+        J = self._joint
+        U, m = self.S * self.P, self.m
+        for a in range(0, U, J["g"]):
+            b = min(U, a + J["g"])
+            ch = kernels.cholesky_inverse(kernels.gram(J["X"], J["beta"][a:b], J["s"][a:b],
+                                                       J["delta"][a:b], batch=b - a))
+            ch.check()
+            if mean_out is not None:
+                out = (mean_out[0][a:b], mean_out[1][a:b])
+                kernels.predict(ch, J["X"], J["Xs"], J["beta"][a:b], J["s"][a:b], J["sp"][a:b],
+                                J["w"][a:b], workspace=J["ws"], out=out)
+                mean = out[0]
+            else:
+                mean = self.mean_dev.permute(0, 2, 1).reshape(U, m)[a:b].contiguous()
+            C = kernels.predict_cov(ch, J["X"], J["Xs"], J["beta"][a:b], J["s"][a:b],
+                                    J["sp"][a:b], J["jit"][a:b], workspace=J["ws"])
+            yield a, b, mean, C
+
+    def _joint_draws(self, seed, offset, nsamp, mean_out=None) -> torch.Tensor:
+        """(nsamp, S, m, P) joint draws: unit u = s P + j reads the normals of stream unit u."""
+        S, P, m = self.S, self.P, self.m
+        out = torch.empty((S * P, nsamp, m), dtype=F64, device=self.model.device)
+        for a, b, mean, C in self._joint_groups(mean_out):
+            info, _ = kernels.cholesky_inplace(C)
+            kernels.check_joint_info(info, a, P, self.joint_jitter)
+            kernels.mvn_draw(C, mean, seed, offset, nsamp, unit0=a, out=out[a:b])
+        return out.reshape(S, P, nsamp, m).permute(2, 0, 3, 1).contiguous()
+
+    def _need_joint(self, what: str) -> None:
+        if getattr(self, "realized", False) != "joint" or self.mean_dev is None:
+            raise ValueError(f"{what} needs a prediction made with realize='joint'")
+
+    def cov(self, to_host: bool = True):
+        """(S, P, m, m): the joint predictive covariance of the m test points per (sample, PC)
+        (``joint_jitter`` s on the diagonal included), computed on demand, a group of units at a
+        time (gp_predict_cov); ``to_host=False`` returns the device tensor."""
+        self._need_joint("cov()")
+        S, P, m = self.S, self.P, self.m
+        if to_host:
+            out = np.empty((S * P, m, m))
+            for a, b, _, C in self._joint_groups():
+                out[a:b] = C.cpu().numpy()
+            return out.reshape(S, P, m, m)
+        out = torch.empty((S * P, m, m), dtype=F64, device=self.model.device)
+        for a, b, _, C in self._joint_groups():
+            out[a:b] = C
+        return out.reshape(S, P, m, m)
+
+    def linear_functional(self, a):
+        """Posterior mean a^T mu and variance a^T C a of a weighted sum over the test points
+        per (sample, PC): ``a`` (m,) gives two (S, P) arrays, ``a`` (k, m) two (k, S, P) arrays
+        (e.g. ``np.full(m, 1 / m)``: the average over the points).  The covariance is formed a
+        group of units at a time and never held for all of them."""
+        self._need_joint("linear_functional()")
+        S, P, m = self.S, self.P, self.m
+        dev = self.model.device
+        A = torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)
+        single = A.dim() == 1
+        A = A.reshape(-1, m)
+        k = A.shape[0]
+        mu = torch.einsum("km,smp->ksp", A, self.mean_dev)
+        var = torch.empty((k, S * P), dtype=F64, device=dev)
+        for lo, hi, _, C in self._joint_groups():
+            var[:, lo:hi] = torch.einsum("ki,uij,kj->ku", A, C, A)
+        var = var.reshape(k, S, P)
+        if single:
+            mu, var = mu[0], var[0]
+        return mu.cpu().numpy(), var.cpu().numpy()
+
+    def _set_results(self, ctx, realize, seed, both, fill: bool = True) -> None:
         """The tail every prediction shares: ``both`` = (mean, var) of the (sample, PC) units in
         s-major order, each (S P, m) (None on the ranks that hold no result) -> the (S, m, P)
         device arrays and the state ``.w`` / ``get_y()`` / ``summary()`` work from."""
@@ -415,6 +563,8 @@ class EmulatorPrediction:
         self._w_dtype = np.dtype(np.float64)
         if both is None:
             self.mean_dev = self.w_dev = self.var_dev = None
+            return
+        if not fill:                      # joint mode fills the arrays after its own chain
             return
         mean_u, var_u = both
         # units are (s, j) in s-major order -> (S, P, m) -> (S, m, P)
@@ -454,10 +604,18 @@ class EmulatorPrediction:
     def get_mu_sigma(self):
         return self.mean, self.var
 
-    def sample_w(self, seed: int | None = None, offset: int = 1) -> np.ndarray:
+    def sample_w(self, seed: int | None = None, offset: int = 1, joint: bool = False,
+                 nsamp: int = 1) -> np.ndarray:
         """A fresh marginal realisation per (sample, point, PC), mean + sqrt(var) N(0, 1), on
-        the device (gp_realize; ``offset`` selects an independent stream for one seed)."""
+        the device (gp_realize; ``offset`` selects an independent stream for one seed).
+        ``joint=True`` (a prediction made with ``realize="joint"``): ``nsamp`` joint draws over
+        the test points per (sample, PC), shape (nsamp, S, m, P) (gp_mvn_draw)."""
         seed = self.seed if seed is None else int(seed)
+        if joint:
+            self._need_joint("sample_w(joint=True)")
+            if int(nsamp) < 1:
+                raise ValueError("nsamp must be at least 1")
+            return self._joint_draws(seed, offset, int(nsamp)).cpu().numpy()
         return kernels.realize(self.mean_dev, self.var_dev, seed, offset).cpu().numpy()
 
     def error_draws(self, rng=None, per_point: bool = True) -> np.ndarray:

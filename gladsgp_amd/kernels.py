@@ -873,3 +873,130 @@ def realize(mean: torch.Tensor, var: torch.Tensor, seed: int, offset: int = 0,
                int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), out.data_ptr(),
                _stream(mean.device))
     return out
+
+
+class JointNotPositiveDefinite(ValueError):
+    """A joint predictive covariance is not numerically positive definite (gp_potrf info > 0):
+    ``units`` lists the failing problems as (index, pivot) pairs."""
+
+    def __init__(self, msg: str, units):
+        super().__init__(msg)
+        self.units = list(units)
+
+
+def check_joint_info(info: torch.Tensor, unit0: int = 0, P: int | None = None,
+                     jitter=None) -> None:
+    """Raise :class:`JointNotPositiveDefinite` for every problem of a joint covariance whose
+    factorisation met a non-positive pivot, naming unit ``unit0 + b`` (as (sample, PC) when
+    ``P`` is given) and the jitter in force; info = -1 is the factorisation's internal error.
+    Synchronises with the device."""
+    vals = info.cpu().tolist()
+    if any(v < 0 for v in vals):
+        check_info(info)
+    bad = [(unit0 + b, v) for b, v in enumerate(vals) if v > 0]
+    if not bad:
+        return
+    name = (lambda u: f"(sample {u // P}, PC {u % P})") if P else (lambda u: f"unit {u}")
+    txt = ", ".join(f"{name(u)} at pivot {v}" for u, v in bad[:8])
+    more = f" and {len(bad) - 8} more" if len(bad) > 8 else ""
+    now = "0" if jitter is None else f"{jitter:g}"
+    raise JointNotPositiveDefinite(
+        f"joint predictive covariance not positive definite for {txt}{more} with "
+        f"joint_jitter = {now} (a multiple of s): raise joint_jitter (1e-8 is the default without "
+        "the prediction nugget; duplicated test points or a test point on a training point need "
+        "one), nothing was retried", bad)
+
+
+def predict_cov(chol: Cholesky, X: torch.Tensor, Xs: torch.Tensor, beta, s, s_pred, jitter=None,
+                out: torch.Tensor | None = None,
+                workspace: Workspace | None = None) -> torch.Tensor:
+    """Joint predictive covariance of the m test points per problem, (batch, m, m), both
+    triangles with the same bits (gp_predict_cov):
+    C = K** + (s_pred + jitter - s) I - (L^-1 K*)^T (L^-1 K*).  ``jitter``: one value per problem
+    added to the diagonal (None = 0).  ``out``: a (batch, m, m) float64 tensor whose last
+    dimension is contiguous (row stride >= m, problem stride >= m rows); only the m x m blocks
+    are written."""
+    L = chol.linv_buf
+    dev = L.device
+    X = _as_f64(X, dev, "X")
+    Xs = _as_f64(Xs, dev, "Xs")
+    n, d = X.shape
+    if n != chol.n:
+        raise ValueError("X rows do not match the factorisation")
+    if Xs.dim() != 2 or Xs.shape[1] != d:
+        raise ValueError(f"Xs: expected (m, {d}), got {tuple(Xs.shape)}")
+    m = Xs.shape[0]
+    batch = L.shape[0]
+    npad = padded_n(n)
+    beta_t = _beta(beta, batch, d, dev)
+    s_t = _per_batch(s, batch, dev, "s")
+    sp_t = _per_batch(s_pred, batch, dev, "s_pred")
+    j_t = None if jitter is None else _per_batch(jitter, batch, dev, "jitter")
+    if out is None:
+        out = torch.empty((batch, m, m), dtype=F64, device=dev)
+    else:
+        _check_device(out, "out")
+        if (out.dtype != F64 or tuple(out.shape) != (batch, m, m) or
+                (m > 1 and (out.stride(2) != 1 or out.stride(1) < m)) or
+                (batch > 1 and m > 0 and out.stride(0) < out.stride(1) * m)):
+            raise ValueError(f"out: expected float64 ({batch}, {m}, {m}) with contiguous rows")
+    if m == 0 or batch == 0:
+        return out
+    ldc = out.stride(1) if m > 1 else max(1, m)
+    nbytes = int(_capi.lib().gp_predict_cov_ws_bytes(n, m, batch))
+    ws = (workspace or _DEFAULT_WS).get(nbytes, dev)
+    _capi.call("gp_predict_cov", L.data_ptr(), L.stride(1), L.stride(0), X.data_ptr(), d,
+               Xs.data_ptr(), d, n, m, d, beta_t.data_ptr(), d, s_t.data_ptr(), sp_t.data_ptr(),
+               j_t.data_ptr() if j_t is not None else None, out.data_ptr(), ldc,
+               out.stride(0) if batch > 1 else ldc * m, batch, ws.data_ptr(), ws.numel(),
+               _stream(dev))
+    return out
+
+
+def cholesky_inplace(A: torch.Tensor):
+    """gp_potrf on a contiguous (batch, n, n) column-major buffer in place: the lower factor in
+    ``A[b, j, i]`` for i >= j, the other triangle untouched.  Returns (info, logdet)."""
+    _check_device(A, "A")
+    if A.dtype != F64 or A.dim() != 3 or A.shape[1] != A.shape[2] or not A.is_contiguous():
+        raise TypeError("A must be a contiguous float64 (batch, n, n) tensor")
+    batch, n, _ = A.shape
+    info = torch.zeros(batch, dtype=torch.int32, device=A.device)
+    logdet = torch.empty(batch, dtype=F64, device=A.device)
+    nbytes = int(_capi.lib().gp_potrf_ws_bytes(n, batch))
+    ws = _potrf_ws(A.device, nbytes)
+    _capi.call("gp_potrf_ws", A.data_ptr(), n, n, n * n, batch, info.data_ptr(),
+               logdet.data_ptr(), ws.data_ptr(), ws.numel(), _stream(A.device))
+    return info, logdet
+
+
+def mvn_draw(R: torch.Tensor, mean, seed: int, offset: int = 0, nsamp: int = 1,
+             unit0: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Joint draws mean + tril(R) xi per problem: (batch, nsamp, m) (gp_mvn_draw).
+
+    ``R`` is the column-major buffer gp_potrf leaves (:func:`cholesky_inplace`), (batch, m, m)
+    with ``R[b, k, i]`` the factor's element (i, k) for i >= k; the other triangle is never read.
+    ``mean`` is (batch, m) or None.  The normals are elements ((unit0 + b) nsamp + r) m + k of
+    gp_realize's stream for (seed, offset), so splitting a batch over calls with matching
+    ``unit0`` gives the bits of one call."""
+    _check_device(R, "R")
+    if R.dtype != F64 or R.dim() != 3 or R.shape[1] != R.shape[2] or not R.is_contiguous():
+        raise TypeError("R must be a contiguous float64 (batch, m, m) tensor")
+    batch, m, _ = R.shape
+    dev = R.device
+    nsamp = int(nsamp)
+    if nsamp < 0 or int(unit0) < 0:
+        raise ValueError("nsamp and unit0 must be non-negative")
+    mean_t = None
+    if mean is not None:
+        mean_t = _as_f64(mean, dev, "mean").reshape(batch, m)
+    if out is None:
+        out = torch.empty((batch, nsamp, m), dtype=F64, device=dev)
+    elif out.dtype != F64 or tuple(out.shape) != (batch, nsamp, m) or not out.is_contiguous():
+        raise ValueError(f"out: expected contiguous float64 ({batch}, {nsamp}, {m})")
+    if m == 0 or nsamp == 0 or batch == 0:
+        return out
+    _capi.call("gp_mvn_draw", R.data_ptr(), max(1, m), m * m, m,
+               mean_t.data_ptr() if mean_t is not None else None, m, nsamp,
+               int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(unit0),
+               out.data_ptr(), max(1, m), batch, _stream(dev))
+    return out

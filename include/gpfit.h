@@ -57,7 +57,7 @@
  *    them ("Operand layouts and the branches they select").  The exceptions, each
  *    reported by its argument number before anything is launched:
  *      - the L^-1 the prediction READS (gp_predict, gp_predict_ex, gp_predict_z,
- *        gp_predict_solve, gp_fit_predict's Linv) and both buffers of gp_pack_linv /
+ *        gp_predict_solve, gp_predict_cov, gp_fit_predict's Linv) and both buffers of gp_pack_linv /
  *        gp_unpack_linv: 16-byte aligned base, even ldinv, even strideInv (gp_potrf_inv,
  *        gp_trtri, gp_trmv, gp_nll and gp_xval take any L^-1 layout);
  *      - every workspace `ws`: 256-byte aligned (gp_dgemm / gp_gemm_ex's split-K scratch and
@@ -697,6 +697,50 @@ int gp_mean_response(const double* X, int n, int d, int ldx, const double* alpha
                      const double* t1, int T1, const double* t2, int T2,
                      const double* Xint, int I, int ldi,
                      double* out, long long lde, long long ldb, hipStream_t stream);
+
+/* Joint predictive covariance of the m test points of a call, per problem b, from the L^-1 of
+ * gp_potrf_inv: what SepiaEmulatorPrediction forms for every (sample, PC) GP before it draws the
+ * PC weights jointly.  With V_b = Linv_b K*_b (n x m; K* the cross-covariance gp_predict uses):
+ *   C_b[i,j] = s_b exp(-sum_k beta_bk (xs_ik - xs_jk)^2) - sum_{r<n} V_b[r,i] V_b[r,j]   (i != j)
+ *   C_b[i,i] = s_pred_b + jitter_b - sum_{r<n} V_b[r,i]^2
+ * (the diagonal's prior term is s_pred_b itself), written column-major at C + b*strideC + i +
+ * j*ldc for i, j < m, both triangles with the same bits (the tiles with J <= I are computed and
+ * mirrored); every other element of the buffer (rows m .. ldc-1, the gaps between problems) is
+ * left untouched.
+ *   Linv     gp_predict's padded contract: 16-B aligned, ldinv >= gp_padded_n(n) and even,
+ *            strideInv even and >= ldinv * gp_padded_n(n).  Column c is taken as zero above row c
+ *            and for rows >= n whatever the buffer holds there.
+ *   X, Xs, beta, s, ldx, ldxs, ldbeta as for gp_predict; 1 <= d <= GPFIT_MAX_DIM.
+ *   jitter   one value per problem added to the diagonal, or NULL (= 0).
+ *   ws       gp_predict_cov_ws_bytes(n, m, batch) bytes, 256-B aligned (K* and V, k-major; 0 when
+ *            n, m or batch is 0, -1 for a negative size).
+ * Each element is one k-ordered fp64 MFMA chain in one workgroup: no atomics, no split-K, equal
+ * inputs give equal bits and a problem's result does not depend on the rest of the batch.
+ * n = 0: the prior, nothing subtracted.  m = 0 or batch = 0: no launch.  Stream-ordered, allocates
+ * nothing, can be captured into a hipGraph.  Argument checks run on the host, in argument order,
+ * before anything is enqueued and return minus the argument's position (-1 .. -19); the
+ * workspace answers with gp_predict's codes, -21 (NULL or misaligned) then -22 (too small). */
+long long gp_predict_cov_ws_bytes(int n, int m, int batch);
+int gp_predict_cov(const double* Linv, int ldinv, long long strideInv, const double* X, int ldx,
+                   const double* Xs, int ldxs, int n, int m, int d, const double* beta,
+                   int ldbeta, const double* s, const double* s_pred, const double* jitter,
+                   double* C, int ldc, long long strideC, int batch, void* ws,
+                   long long ws_bytes, hipStream_t stream);
+
+/* Joint draws from N(mean_b, R_b R_b^T), R_b the lower factor gp_potrf left in C_b (column-major,
+ * ldr, strideR):
+ *   out[(b*nsamp + r)*ldo + i] = mean[b*ldm + i] + sum_{k<=i} R_b[i,k] xi_e,
+ *   e = ((unit0 + b)*nsamp + r)*m + k,
+ * xi_e element e of gp_realize's normal stream for (seed, offset): Philox4x32-10 at counter
+ * (e/2, offset), Box-Muller, cos for even e and sin for odd e.  unit0 is the index of problem 0
+ * in the caller's stream of problems, so a batch split over several calls with matching unit0
+ * gives the bits of one call.  The strict upper triangle of R is never read (gp_potrf leaves the
+ * upper half of C there).  mean may be NULL (= 0).  0 <= nsamp <= 262144; R is read once per
+ * group of 8 draws.  m = 0, nsamp = 0 or batch = 0: no launch.  Stream-ordered, allocates
+ * nothing, can be captured into a hipGraph.  A violation returns minus its argument position. */
+int gp_mvn_draw(const double* R, int ldr, long long strideR, int m, const double* mean, int ldm,
+                int nsamp, unsigned long long seed, unsigned long long offset, long long unit0,
+                double* out, long long ldo, int batch, hipStream_t stream);
 
 /* PCA truncation-error curve: the residual sums of every requested truncation rank in one pass
  * over the ensemble (plot_PC_RMSE.py:25-46,84-108: compute_truncation_error of the rank-k field
