@@ -363,6 +363,7 @@ class EmulatorPrediction:
     """
 
     joint_max_points = 4096
+    joint_jitter_default = 1e-8     # without the prediction nugget, a multiple of s
 
     def __init__(self, model: EmulatorModel = None, samples: dict = None, t_pred=None,
                  pred_nugget: bool = True, ctx: gdist.Context | None = None,
@@ -451,8 +452,8 @@ class EmulatorPrediction:
         self.shard = "units"
         self.lamWOs = np.asarray(samples["lamWOs"], dtype=np.float64).reshape(S)
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)  # noqa
-        self.joint_jitter = float((0.0 if pred_nugget else 1e-8) if joint_jitter is None
-                                  else joint_jitter)
+        self.joint_jitter = float((0.0 if pred_nugget else self.joint_jitter_default)
+                                  if joint_jitter is None else joint_jitter)
         w_hat = model.w_hat.transpose(0, 1).contiguous()       # (P, n)
         n = model.n
         npad = kernels.padded_n(n)

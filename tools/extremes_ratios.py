@@ -1,11 +1,13 @@
 """Print DESIGN.md section 7's tables: the measured error / noise of every chain quantity per
 (regime, n), worst over the entry points that produce it and over the factorisation paths, from
 the helpers of tests/test_gpu_extremes.py; then the same for the PCA front end (statistics,
-eigensolver, randomized SVD, weights) from tests/test_gpu_pca_extremes.py.  Needs a HIP device.
-Entries above 16 also show, in parentheses, 16 error / bound with the documented term: they must
-be in tests/_mp_ref.FINDINGS or tests/_mp_pca_ref.FINDINGS.
+eigensolver, randomized SVD, weights) from tests/test_gpu_pca_extremes.py, and for the joint
+covariance, its factor and the joint draws from tests/test_gpu_joint_extremes.py.  Needs a HIP
+device.  Entries above 16 also show, in parentheses, 16 error / bound with the documented term:
+they must be in tests/_mp_ref.FINDINGS, tests/_mp_pca_ref.FINDINGS or
+tests/_mp_joint_ref.FINDINGS_COV.
 
-    python tools/extremes_ratios.py [chain|pca]
+    python tools/extremes_ratios.py [chain|pca|joint]
 """
 import os
 import sys
@@ -93,14 +95,63 @@ def pca(dev):
         print(f"| {regime} | {fmt(_worst(*e['w_hat']))} | {fmt(_worst(*e['LamSim']))} |")
 
 
+def joint(dev):
+    """The joint covariance, its factor and the draws (tests/test_gpu_joint_extremes.py)."""
+    import _mp_joint_ref as J
+    import test_gpu_joint_extremes as TJ
+    cols = [f"{n} {pts}" for n, pts in J.CASES]
+    print("\n| C: regime | " + " | ".join(cols) + " |")
+    print("|---|" + "---|" * len(cols))
+    for regime in M.REGIMES:
+        cells = []
+        for n, pts in J.CASES:
+            err, _ = TJ.cov_errors(dev, regime, n, pts)
+            nz, lim = J.noise_cov(regime, n, pts), J.limit_cov(regime, n, pts)
+            cell = fmt(err / nz)
+            if err > M.MARGIN * nz:
+                cell += f" ({fmt(M.MARGIN * err / lim)})"
+                if (regime, n) not in J.FINDINGS_COV:
+                    cell += " NOT A DOCUMENTED FINDING"
+            cells.append(cell)
+        print(f"| {regime} | " + " | ".join(cells) + " |")
+    cases = [(n, pts, ng) for n, pts in TJ.FACTOR_CASES for ng in (True, False)]
+    print("\n| R, logdet: regime | " +
+          " | ".join(f"{pts} {'nugget' if ng else 'jitter'}" for _, pts, ng in cases) + " |")
+    print("|---|" + "---|" * len(cases))
+    for regime in M.REGIMES:
+        cells = []
+        for n, pts, ng in cases:
+            (eR, nR), (eld, nld) = TJ.factor_errors(dev, regime, n, pts, ng)
+            cells.append(f"{fmt(eR / nR)}, {fmt(eld / nld)}")
+        print(f"| {regime} | " + " | ".join(cells) + " |")
+    print("\n| default jitter 1e-8 s at (n, m) = (130, 130): regime | derived sufficient / s | "
+          "info | draws finite |")
+    print("|---|---|---|---|")
+    for group in M.GROUPS:
+        for regime, derived, info, finite in TJ.default_jitter_run(dev, group):
+            print(f"| {regime} | {derived:.2e} | {info} | {finite} |")
+    print("\n| draws: m | " + " | ".join(f"nsamp {k}: error / noise, / bound, / per-element bound"
+                                         for k in (1, 8, 9)) + " |")
+    print("|---|---|---|---|")
+    for m in (1, 63, 64, 65, 257):
+        cells = []
+        for nsamp in (1, 8, 9):
+            err, bound, nz, tight = TJ.draw_errors(dev, m, nsamp)
+            cells.append(f"{fmt(float(np.max(err / nz)))}, {fmt(float(np.max(err / bound)))}, "
+                         f"{fmt(float(np.max(err / tight)))}")
+        print(f"| {m} | " + " | ".join(cells) + " |")
+
+
 def main():
     from gladsgp_amd import kernels  # noqa: F401 (loads libgpfit.so)
     dev = torch.device("cuda:0")
-    which = sys.argv[1] if len(sys.argv) > 1 else "both"
-    if which in ("chain", "both"):
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which in ("chain", "all", "both"):
         chain(dev)
-    if which in ("pca", "both"):
+    if which in ("pca", "all", "both"):
         pca(dev)
+    if which in ("joint", "all"):
+        joint(dev)
 
 
 if __name__ == "__main__":
