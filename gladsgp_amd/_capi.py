@@ -94,6 +94,13 @@ SIGNATURES = {
     "gp_mcmc_group_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "gp_mcmc_ens_prep": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "gp_mcmc_ens_decide": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                   c_void_p]),
+    "gp_mcmc_ens_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
     "gp_realize": (c_int, [c_void_p, c_void_p, c_ll, ctypes.c_ulonglong, ctypes.c_ulonglong,
                            c_void_p, c_void_p]),
     "gp_dgemm_ws_bytes": (c_ll, [c_int, c_int, c_int]),
@@ -260,15 +267,24 @@ def exported_symbols() -> list[str]:
 
 
 MCMC_MAX_GROUP = 4            # GPFIT_MCMC_MAX_GROUP
+MCMC_MAX_CHAINS = 4096        # GPFIT_MCMC_MAX_CHAINS
 MCMC_DIST = {"Gamma": 0, "Beta": 1, "Normal": 2, "Uniform": 3}
 MCMC_STEP = {"Uniform": 0, "BetaRho": 1}
 
 
+MCMC_POINTERS = ("betaU", "lamUz", "lamWs", "lamWOs", "ll", "lam", "u", "step_betaU",
+                 "step_lamUz", "step_lamWs", "step_lamWOs", "acc", "lp", "scratch")
+
+
+class McmcStrides(ctypes.Structure):
+    """gp_mcmc_strides (include/gpfit.h): chain-to-chain element stride of each pointer field of
+    gp_mcmc_state, for the gp_mcmc_ens_* calls."""
+    _fields_ = [(nm, c_ll) for nm in MCMC_POINTERS]
+
+
 class McmcState(ctypes.Structure):
     """gp_mcmc_state (include/gpfit.h): the sampler's device buffers and priors."""
-    _fields_ = [(nm, c_void_p) for nm in (
-        "betaU", "lamUz", "lamWs", "lamWOs", "ll", "lam", "u", "step_betaU", "step_lamUz",
-        "step_lamWs", "step_lamWOs", "acc", "lp", "scratch")] + [
+    _fields_ = [(nm, c_void_p) for nm in MCMC_POINTERS] + [
         ("P", c_int), ("d", c_int), ("dist", c_int * 4), ("steptype", c_int * 4),
         ("pa", ctypes.c_double * 4), ("pb", ctypes.c_double * 4), ("lo", ctypes.c_double * 4),
         ("hi", ctypes.c_double * 4)]

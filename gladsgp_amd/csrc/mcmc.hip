@@ -15,6 +15,9 @@
 //                         on the sum), state, per-GP likelihood and acceptance counters in place,
 //                         and for the sweep's last group the log posterior
 //   gp_mcmc_group_step    one group's decide and the next group's prep in one launch
+//   gp_mcmc_ens_prep / _decide / _step   the same three for an ensemble of chains that share
+//                         X, P, priors, bounds and step types (mcmc.EnsembleSampler): one
+//                         workgroup per chain runs the single-chain code on that chain's buffers
 // They replace some 100 elementwise launches per group of the tensor-op form of the same sweep
 // (mcmc.py _sweep_torch, kept as the host-logic reference the CPU tests run).  Arithmetic is
 // op-for-op that form's (no FMA contraction), so the chains agree with it and with the oracle
@@ -58,29 +61,50 @@ GP_DEV double log_prior(const gp_mcmc_state& S, int p, double x) {
   }
 }
 
+// The device buffers of the chain a workgroup runs: gp_mcmc_state's pointers as they are (the
+// single-chain kernels) or moved by chain c's strides (the ensemble kernels).  The bodies below
+// read every pointer from here and P, d and the priors from the launch's gp_mcmc_state.
+struct ChainPtrs {
+  double *betaU, *lamUz, *lamWs, *lamWOs, *ll;
+  const double *lam, *u, *step_betaU, *step_lamUz, *step_lamWs, *step_lamWOs;
+  double *acc, *lp, *scratch;
+};
+
+GP_DEV ChainPtrs chain_ptrs(const gp_mcmc_state& S) {
+  return {S.betaU, S.lamUz, S.lamWs, S.lamWOs, S.ll, S.lam, S.u, S.step_betaU, S.step_lamUz,
+          S.step_lamWs, S.step_lamWOs, S.acc, S.lp, S.scratch};
+}
+
+GP_DEV ChainPtrs chain_ptrs(const gp_mcmc_state& S, const gp_mcmc_strides& T, long long c) {
+  return {S.betaU + c * T.betaU, S.lamUz + c * T.lamUz, S.lamWs + c * T.lamWs,
+          S.lamWOs + c * T.lamWOs, S.ll + c * T.ll, S.lam + c * T.lam, S.u + c * T.u,
+          S.step_betaU + c * T.step_betaU, S.step_lamUz + c * T.step_lamUz,
+          S.step_lamWs + c * T.step_lamWs, S.step_lamWOs + c * T.step_lamWOs,
+          S.acc + c * T.acc, S.lp + c * T.lp, S.scratch + c * T.scratch};
+}
+
 // current value, step and uniforms of update `code` for element j (j = 0 for lamWOs)
-GP_DEV void update_refs(const gp_mcmc_state& S, int code, int j, double*& cur, double& step,
-                        double& up, double& ua) {
-  const int P = S.P, d = S.d;
+GP_DEV void update_refs(const ChainPtrs& Q, int P, int d, int code, int j, double*& cur,
+                        double& step, double& up, double& ua) {
   const long long off = 2LL * P * code;
   if (code <= d) {
-    cur = S.betaU + (long long)code * P + j;
-    step = S.step_betaU[(long long)code * P + j];
+    cur = Q.betaU + (long long)code * P + j;
+    step = Q.step_betaU[(long long)code * P + j];
   } else if (code == d + 1) {
-    cur = S.lamUz + j;
-    step = S.step_lamUz[j];
+    cur = Q.lamUz + j;
+    step = Q.step_lamUz[j];
   } else if (code == d + 2) {
-    cur = S.lamWs + j;
-    step = S.step_lamWs[j];
+    cur = Q.lamWs + j;
+    step = Q.step_lamWs[j];
   } else {
-    cur = S.lamWOs;
-    step = S.step_lamWOs[0];
-    up = S.u[off];
-    ua = S.u[off + 1];
+    cur = Q.lamWOs;
+    step = Q.step_lamWOs[0];
+    up = Q.u[off];
+    ua = Q.u[off + 1];
     return;
   }
-  up = S.u[off + j];
-  ua = S.u[off + P + j];
+  up = Q.u[off + j];
+  ua = Q.u[off + P + j];
 }
 
 // proposal of parameter p from x (mcmc.propose): candidate (x when rejected by the bounds or
@@ -100,13 +124,13 @@ GP_DEV void propose(const gp_mcmc_state& S, int p, double x, double step, double
   dlp = log_prior(S, p, cand) - log_prior(S, p, x);
 }
 
-GP_DEV void prep_body(const GroupArgs& A, double* __restrict__ beta, double* __restrict__ s,
-                      double* __restrict__ delta) {
+GP_DEV void prep_body(const GroupArgs& A, const ChainPtrs& Q, double* __restrict__ beta,
+                      double* __restrict__ s, double* __restrict__ delta) {
   const gp_mcmc_state& S = A.S;
   const int j = threadIdx.x, P = S.P, d = S.d;
-  double* cand = S.scratch;                               // [i][P]
-  double* okf = S.scratch + GPFIT_MCMC_MAX_GROUP * P;
-  double* dlp = S.scratch + 2 * GPFIT_MCMC_MAX_GROUP * P;
+  double* cand = Q.scratch;                               // [i][P]
+  double* okf = Q.scratch + GPFIT_MCMC_MAX_GROUP * P;
+  double* dlp = Q.scratch + 2 * GPFIT_MCMC_MAX_GROUP * P;
   // The prior-only move of betaU row 0 and the group's g proposals are independent (each reads
   // the current state of its own element only; the Gram inputs below never read row 0), so
   // thread t runs row 0's element t (t < P) or update t / P - 1's element t % P: one chain of
@@ -117,19 +141,19 @@ GP_DEV void prep_body(const GroupArgs& A, double* __restrict__ beta, double* __r
     if (i < 0) {                                          // betaU row 0: prior only
       if (!A.flag) continue;
       double *cur, step, up, ua;
-      update_refs(S, 0, e, cur, step, up, ua);
+      update_refs(Q, P, d, 0, e, cur, step, up, ua);
       double c, dl;
       bool ok;
       propose(S, 0, *cur, step, up, c, ok, dl);
       const bool acc = ok && (log(ua) < dl);
       if (acc) *cur = c;
-      S.acc[e] += acc ? 1.0 : 0.0;
+      Q.acc[e] += acc ? 1.0 : 0.0;
       continue;
     }
     const int code = A.kinds[i];
     if (code == d + 3 && e > 0) continue;                 // lamWOs: one element
     double *cur, step, up, ua;
-    update_refs(S, code, e, cur, step, up, ua);
+    update_refs(Q, P, d, code, e, cur, step, up, ua);
     double c, dl;
     bool ok;
     propose(S, param_of(code, d), *cur, step, up, c, ok, dl);
@@ -139,14 +163,14 @@ GP_DEV void prep_body(const GroupArgs& A, double* __restrict__ beta, double* __r
   }
   __syncthreads();
   if (j >= P) return;
-  const double lam = S.lam[j];
+  const double lam = Q.lam[j];
   for (int i = 0; i < A.g; ++i) {
     for (int pat = 0; pat < (1 << i); ++pat) {
       const int slot = (1 << i) - 1 + pat;
       const long long row = (long long)slot * P + j;
-      double lUz = S.lamUz[j], lWs = S.lamWs[j], lWO = S.lamWOs[0];
+      double lUz = Q.lamUz[j], lWs = Q.lamWs[j], lWO = Q.lamWOs[0];
       for (int r = 1; r <= d; ++r) {
-        double v = S.betaU[(long long)r * P + j];
+        double v = Q.betaU[(long long)r * P + j];
         for (int q = 0; q <= i; ++q)
           if ((q == i || ((pat >> q) & 1)) && A.kinds[q] == r) v = cand[q * P + j];
         beta[row * d + (r - 1)] = v;
@@ -164,12 +188,13 @@ GP_DEV void prep_body(const GroupArgs& A, double* __restrict__ beta, double* __r
   }
 }
 
-GP_DEV void decide_body(const GroupArgs& A, const double* __restrict__ ll_all) {
+GP_DEV void decide_body(const GroupArgs& A, const ChainPtrs& Q,
+                        const double* __restrict__ ll_all) {
   const gp_mcmc_state& S = A.S;
   const int j = threadIdx.x, P = S.P, d = S.d;
-  const double* cand = S.scratch;
-  const double* okf = S.scratch + GPFIT_MCMC_MAX_GROUP * P;
-  const double* dlp = S.scratch + 2 * GPFIT_MCMC_MAX_GROUP * P;
+  const double* cand = Q.scratch;
+  const double* okf = Q.scratch + GPFIT_MCMC_MAX_GROUP * P;
+  const double* dlp = Q.scratch + 2 * GPFIT_MCMC_MAX_GROUP * P;
   __shared__ double sh[1024];
   __shared__ int sh_acc;
   int pat = 0;
@@ -178,30 +203,30 @@ GP_DEV void decide_body(const GroupArgs& A, const double* __restrict__ ll_all) {
     const double lln = j < P ? ll_all[((long long)(1 << i) - 1 + pat) * P + j] : 0.0;
     bool acc = false;
     if (code == d + 3) {                       // lamWOs: one decision on the sum over GPs
-      if (j < P) sh[j] = lln - S.ll[j];
+      if (j < P) sh[j] = lln - Q.ll[j];
       __syncthreads();
       if (j == 0) {
         double sum = 0.0;
         for (int q = 0; q < P; ++q) sum += sh[q];
         double *cur, step, up, ua;
-        update_refs(S, code, 0, cur, step, up, ua);
+        update_refs(Q, P, d, code, 0, cur, step, up, ua);
         const bool a = okf[i * P] != 0.0 && (log(ua) < sum + dlp[i * P]);
         if (a) *cur = cand[i * P];
-        S.acc[(long long)code * P] += a ? 1.0 : 0.0;
+        Q.acc[(long long)code * P] += a ? 1.0 : 0.0;
         sh_acc = a;
       }
       __syncthreads();
       acc = sh_acc != 0;
-      if (acc && j < P) S.ll[j] = lln;
+      if (acc && j < P) Q.ll[j] = lln;
     } else if (j < P) {
       double *cur, step, up, ua;
-      update_refs(S, code, j, cur, step, up, ua);
-      acc = okf[i * P + j] != 0.0 && (log(ua) < lln - S.ll[j] + dlp[i * P + j]);
+      update_refs(Q, P, d, code, j, cur, step, up, ua);
+      acc = okf[i * P + j] != 0.0 && (log(ua) < lln - Q.ll[j] + dlp[i * P + j]);
       if (acc) {
         *cur = cand[i * P + j];
-        S.ll[j] = lln;
+        Q.ll[j] = lln;
       }
-      S.acc[(long long)code * P + j] += acc ? 1.0 : 0.0;
+      Q.acc[(long long)code * P + j] += acc ? 1.0 : 0.0;
     }
     pat |= (acc ? 1 : 0) << i;
     __syncthreads();
@@ -215,39 +240,39 @@ GP_DEV void decide_body(const GroupArgs& A, const double* __restrict__ ll_all) {
   if (nt <= kLpTerms) {
     for (int t = j; t < nt; t += blockDim.x) {
       const int q = t / P, e = t - q * P;
-      terms[t] = q <= d ? log_prior(S, 0, S.betaU[(long long)q * P + e])
-                        : (q == d + 1 ? log_prior(S, 1, S.lamUz[e]) : log_prior(S, 2, S.lamWs[e]));
+      terms[t] = q <= d ? log_prior(S, 0, Q.betaU[(long long)q * P + e])
+                        : (q == d + 1 ? log_prior(S, 1, Q.lamUz[e]) : log_prior(S, 2, Q.lamWs[e]));
     }
     __syncthreads();
     if (j < P) {
-      double t = S.ll[j];
+      double t = Q.ll[j];
       for (int q = 0; q < d + 3; ++q) t += terms[q * P + j];
       sh[j] = t;
     }
   } else if (j < P) {
-    double t = S.ll[j];
-    for (int r = 0; r <= d; ++r) t += log_prior(S, 0, S.betaU[(long long)r * P + j]);
-    t += log_prior(S, 1, S.lamUz[j]);
-    t += log_prior(S, 2, S.lamWs[j]);
+    double t = Q.ll[j];
+    for (int r = 0; r <= d; ++r) t += log_prior(S, 0, Q.betaU[(long long)r * P + j]);
+    t += log_prior(S, 1, Q.lamUz[j]);
+    t += log_prior(S, 2, Q.lamWs[j]);
     sh[j] = t;
   }
   __syncthreads();
   if (j == 0) {
     double sum = 0.0;
     for (int q = 0; q < P; ++q) sum += sh[q];
-    S.lp[0] = sum + log_prior(S, 3, S.lamWOs[0]);
+    Q.lp[0] = sum + log_prior(S, 3, Q.lamWOs[0]);
   }
 }
 
 __global__ __launch_bounds__(1024) void mcmc_prep_kernel(GroupArgs A, double* __restrict__ beta,
                                                          double* __restrict__ s,
                                                          double* __restrict__ delta) {
-  prep_body(A, beta, s, delta);
+  prep_body(A, chain_ptrs(A.S), beta, s, delta);
 }
 
 __global__ __launch_bounds__(1024) void mcmc_decide_kernel(GroupArgs A,
                                                            const double* __restrict__ ll_all) {
-  decide_body(A, ll_all);
+  decide_body(A, chain_ptrs(A.S), ll_all);
 }
 
 // A group's decisions, then the next group's proposals and Gram inputs, in one launch (the
@@ -257,9 +282,61 @@ __global__ __launch_bounds__(1024) void mcmc_step_kernel(GroupArgs D,
                                                          GroupArgs A, double* __restrict__ beta,
                                                          double* __restrict__ s,
                                                          double* __restrict__ delta) {
-  decide_body(D, ll_all);
+  decide_body(D, chain_ptrs(D.S), ll_all);
   __syncthreads();
-  prep_body(A, beta, s, delta);
+  prep_body(A, chain_ptrs(A.S), beta, s, delta);
+}
+
+// The ensemble forms: workgroup c runs the same bodies on chain c's buffers (the state's
+// pointers moved by c strides) and on chain c's rows of the chain-major batch, which start at
+// c (2^g - 1) P.  No workgroup reads or writes another chain's memory, so a chain's results do
+// not depend on the others of the launch, and a chain's arithmetic is the single-chain kernels'.
+GP_DEV long long chain_rows(const GroupArgs& A) {
+  return (long long)blockIdx.x * ((1LL << A.g) - 1) * A.S.P;
+}
+
+__global__ __launch_bounds__(1024) void mcmc_ens_prep_kernel(GroupArgs A, gp_mcmc_strides T,
+                                                             double* __restrict__ beta,
+                                                             double* __restrict__ s,
+                                                             double* __restrict__ delta) {
+  const long long r = chain_rows(A);
+  prep_body(A, chain_ptrs(A.S, T, blockIdx.x), beta + r * A.S.d, s + r, delta + r);
+}
+
+__global__ __launch_bounds__(1024) void mcmc_ens_decide_kernel(GroupArgs A, gp_mcmc_strides T,
+                                                               const double* __restrict__ ll_all) {
+  decide_body(A, chain_ptrs(A.S, T, blockIdx.x), ll_all + chain_rows(A));
+}
+
+__global__ __launch_bounds__(1024) void mcmc_ens_step_kernel(GroupArgs D, gp_mcmc_strides T,
+                                                             const double* __restrict__ ll_all,
+                                                             GroupArgs A,
+                                                             double* __restrict__ beta,
+                                                             double* __restrict__ s,
+                                                             double* __restrict__ delta) {
+  decide_body(D, chain_ptrs(D.S, T, blockIdx.x), ll_all + chain_rows(D));
+  __syncthreads();
+  const long long r = chain_rows(A);
+  prep_body(A, chain_ptrs(A.S, T, blockIdx.x), beta + r * A.S.d, s + r, delta + r);
+}
+
+// 0, or 1 when the strides are unusable: none given, or with more than one chain a negative
+// stride, or one below the per-chain extent of a buffer the kernels write (chains would share
+// or overlap elements they write).  One chain never uses them.
+int bad_strides(const gp_mcmc_strides* T, int nchains, int P, int d) {
+  if (!T) return 1;
+  if (nchains == 1) return 0;
+  const long long ro[] = {T->lam, T->u, T->step_betaU, T->step_lamUz, T->step_lamWs,
+                          T->step_lamWOs};
+  for (long long v : ro)
+    if (v < 0) return 1;
+  const long long written[][2] = {{T->betaU, (long long)(d + 1) * P}, {T->lamUz, P},
+                                  {T->lamWs, P}, {T->lamWOs, 1}, {T->ll, P},
+                                  {T->acc, (long long)(d + 4) * P}, {T->lp, 1},
+                                  {T->scratch, 3LL * GPFIT_MCMC_MAX_GROUP * P}};
+  for (const auto& w : written)
+    if (w[0] < w[1]) return 1;
+  return 0;
 }
 
 int group_args(const gp_mcmc_state* S, const int* kinds, int g, int flag, GroupArgs& A) {
@@ -323,6 +400,58 @@ extern "C" int gp_mcmc_group_decide(const gp_mcmc_state* S, const int* kinds, in
   if (rc) return rc;
   if (!ll_all) return -7;
   hipLaunchKernelGGL(mcmc_decide_kernel, dim3(1), dim3(block_for(S->P)), 0, stream, A, ll_all);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}
+
+extern "C" int gp_mcmc_ens_prep(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
+                                int nchains, const int* kinds, int g, int first, double* beta,
+                                double* s, double* delta, hipStream_t stream) {
+  GroupArgs A;
+  const int rc = group_args(S, kinds, g, first, A);
+  if (rc) return rc;
+  if (!beta || !s || !delta) return -7;
+  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
+  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
+  hipLaunchKernelGGL(mcmc_ens_prep_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, A,
+                     *strides, beta, s, delta);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}
+
+extern "C" int gp_mcmc_ens_decide(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
+                                  int nchains, const int* kinds, int g, int last,
+                                  const double* ll_all, hipStream_t stream) {
+  GroupArgs A;
+  const int rc = group_args(S, kinds, g, last, A);
+  if (rc) return rc;
+  if (!ll_all) return -7;
+  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
+  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
+  hipLaunchKernelGGL(mcmc_ens_decide_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, A,
+                     *strides, ll_all);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}
+
+extern "C" int gp_mcmc_ens_step(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
+                                int nchains, const int* kinds, int g, int last,
+                                const double* ll_all, const gp_mcmc_state* S_next,
+                                const int* kinds_next, int g_next, int first, double* beta,
+                                double* s, double* delta, hipStream_t stream) {
+  GroupArgs D, A;
+  int rc = group_args(S, kinds, g, last, D);
+  if (rc) return rc;
+  if (!ll_all) return -7;
+  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
+  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
+  rc = group_args(S_next, kinds_next, g_next, first, A);
+  if (rc) return rc - 10;
+  if (!beta || !s || !delta) return -17;
+  if (S_next->P != S->P) return -18;
+  if (bad_strides(strides, nchains, S_next->P, S_next->d)) return -19;
+  hipLaunchKernelGGL(mcmc_ens_step_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, D,
+                     *strides, ll_all, A, beta, s, delta);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
 }

@@ -36,9 +36,16 @@ draws agree in distribution, not number for number.  ``.mean`` always holds the 
 513): ``get_y()`` then reconstructs from the assigned values and returns that dtype.  All
 arithmetic runs in libgpfit (fp64); the (sample, PC) pairs are one batched Gram ->
 Cholesky/L^-1 -> predict.
+
+Repeat chains (``EmulatorModel.do_mcmc_chains``, the run of mcmc_diagnostics_advanced.py:50-54):
+chain 0 starts at the current values; every later chain, unless the caller gives its start,
+starts at the current values with each element multiplied by exp(0.5 z), z ~ N(0, 1) from
+``model.rng``, clipped into the parameter's bounds.  This dispersed-start rule is *unpinned*:
+SEPIA's own restart rule (``do_mcmc(no_init=False)``) cannot be checked offline.
 """
 from __future__ import annotations
 
+import copy
 import os
 
 import numpy as np
@@ -229,6 +236,47 @@ class EmulatorModel:
         else:
             self.samples = {k: np.concatenate([self.samples[k], new[k]]) for k in new}
 
+    def do_mcmc_chains(self, nsamp, nchains, starts=None, seeds=None):
+        """``nchains`` chains of this model in one ensemble (mcmc.EnsembleSampler), ``nsamp``
+        sweeps each, stored as ``self.chains``: betaU (C, N, (d+1) P), lamUz / lamWs (C, N, P),
+        lamWOs / logPost (C, N, 1).  ``samples``, the current parameter values and ``do_mcmc``
+        are untouched.  Chain 0 starts at the current values; chain c > 0 at ``starts[c]`` (a
+        dict name -> values) if given, otherwise at the dispersed start of the module doc.
+        Chain c draws from ``np.random.default_rng(seeds[c])``; by default the seeds are spawned
+        from ``self.rng``.  This is the repeat-chain run of mcmc_diagnostics_advanced.py:50-54;
+        ``chain_diagnostics`` gives R-hat and the effective sample size of the result."""
+        C = int(nchains)
+        plist = []
+        for c in range(C):
+            pr = copy.deepcopy(self.params)
+            if c > 0:
+                for k in ModelParams.names:
+                    p = getattr(pr, k)
+                    if starts is not None and starts[c] is not None:
+                        pr[k] = starts[c][k]
+                    else:
+                        z = self.rng.standard_normal(p.val_shape)
+                        p.val = np.clip(p.val * np.exp(0.5 * z), p.bounds[0], p.bounds[1])
+            plist.append(pr)
+        if seeds is None:
+            seeds = self.rng.bit_generator.seed_seq.spawn(C)
+        if len(seeds) != C:
+            raise ValueError(f"{len(seeds)} seeds for {C} chains")
+        w = self.w_hat.transpose(0, 1).contiguous()                     # (P, n)
+        sm = mcmc.EnsembleSampler(self.data.sim_data.t_dev, w[None].expand(C, -1, -1),
+                                  self.LamSim.reshape(1, -1).expand(C, -1), plist)
+        self.chains = sm.run(int(nsamp), [np.random.default_rng(s) for s in seeds])
+        return self.chains
+
+    def chain_diagnostics(self, nburn=0) -> dict:
+        """Split-R-hat and effective sample size of ``self.chains`` after ``nburn`` draws
+        (mcmc.rhat / mcmc.ess): {"rhat": {name: (width,)}, "ess": {name: (width,)}} for betaU,
+        lamUz, lamWs, lamWOs and logPost."""
+        if getattr(self, "chains", None) is None:
+            raise ValueError("model has no chains (do_mcmc_chains first)")
+        return {"rhat": {k: mcmc.rhat(v, nburn) for k, v in self.chains.items()},
+                "ess": {k: mcmc.ess(v, nburn) for k, v in self.chains.items()}}
+
     @property
     def w_hat(self) -> torch.Tensor:
         """(n, P) PC weights of the training runs."""
@@ -285,6 +333,41 @@ class EmulatorModel:
         ch.check()
         w = self.w_hat.transpose(0, 1).contiguous()           # (P, n)
         return -float(kernels.nll(ch, w).sum().item())
+
+
+def fit_ensemble(models, n_burn, n_levels, nsamp, tune=True):
+    """Tune and sample a list of EmulatorModels on one design together: the drop-in for the
+    inner loop of fit_scalar_models.py:457-473 (16 scalar emulators per ensemble size, each a
+    ``tune_step_sizes(100, 10)`` + ``do_mcmc(512)``), as one mcmc.EnsembleSampler whose every
+    gp_loglik call carries all models' problems.  The models must share ``t``, P and the priors,
+    bounds and step types (ValueError names the field that differs); each is driven by its own
+    ``model.rng`` and ends with ``samples``, parameter values, step sizes and ``tune_info`` as if
+    it had run ``tune_step_sizes(n_burn, n_levels)`` + ``do_mcmc(nsamp)`` alone."""
+    models = list(models)
+    if not models:
+        return models
+    X = models[0].data.sim_data.t_dev
+    mcmc.check_shared_priors([m.params for m in models])
+    for c, m in enumerate(models[1:], start=1):
+        if m.data.sim_data.t_dev.shape != X.shape or not torch.equal(m.data.sim_data.t_dev, X):
+            raise ValueError(f"ensemble: model {c} differs from model 0 in t (the design)")
+    w = torch.stack([m.w_hat.transpose(0, 1) for m in models]).contiguous()      # (C, P, n)
+    lam = torch.stack([m.LamSim.reshape(-1) for m in models])
+    sm = mcmc.EnsembleSampler(X, w, lam, [m.params for m in models])
+    rngs = [m.rng for m in models]
+    if tune:
+        mcmc.tune_step_sizes_ensemble(sm, int(n_burn), int(n_levels), rngs)
+        for m, info in zip(models, sm.last_tune):
+            m.tune_info = info
+        sm.write_back()
+        sm.init_state()             # do_mcmc starts a sampler from the written-back values
+    new = sm.run(int(nsamp), rngs)
+    sm.write_back()
+    for c, m in enumerate(models):
+        mine = {k: v[c] for k, v in new.items()}
+        m.samples = mine if m.samples is None else {
+            k: np.concatenate([m.samples[k], mine[k]]) for k in mine}
+    return models
 
 
 def gp_params(samples, LamSim, d, P, pred_nugget=True):

@@ -633,28 +633,18 @@ def logistic_step(log_steps: np.ndarray, accepts: np.ndarray, trials: int,
     return float(np.exp((target_logit - b0) / b1))
 
 
-def tune_step_sizes(sampler: GPUSampler, n_burn: int, n_levels: int,
-                    rng: np.random.Generator) -> None:
-    """GPMSA-style step-size tuning (see module doc); updates params' mcmcStepParam in place
-    and leaves the sampler's chain at the state reached."""
-    pr = sampler.params
-    if sampler.st is None:
-        sampler.init_state()
-    ex = np.linspace(-(n_levels - 1) / 2.0, (n_levels - 1) / 2.0, n_levels)
-    base = {k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
-    # burn-in at the default steps first: acceptance counted while the chain is still
-    # travelling from the start values would make the smallest-step level look worst
-    sampler.set_steps(1.0)
-    sampler.run(n_burn, rng, record=False)
-    counts = []
-    for e in ex:
-        sampler.set_steps(2.0 ** e)
-        sampler.reset_counts()
-        sampler.run(n_burn, rng, record=False)
-        counts.append(sampler.counts())
+def _ladder(n_levels: int) -> np.ndarray:
+    """Step-scale exponents of the tuning ladder: n_levels evenly spaced around 0."""
+    return np.linspace(-(n_levels - 1) / 2.0, (n_levels - 1) / 2.0, n_levels)
+
+
+def _fit_chain_steps(pr: ModelParams, base: dict, ex: np.ndarray, counts: list, n_burn: int):
+    """The per-element logistic fits of one chain (tune_step_sizes and
+    tune_step_sizes_ensemble): ``counts`` holds one sampler.counts() dict per ladder level,
+    ``base`` the steps the ladder scaled.  Returns (new steps per parameter, the tune record)."""
     logs = {k: np.log(base[k][None] * (2.0 ** ex).reshape((-1,) + (1,) * base[k].ndim))
             for k in base}
-    P, d = sampler.P, sampler.d
+    d, P = pr.betaU.val_shape[0] - 1, pr.betaU.val_shape[1]
     new = {k: base[k].copy() for k in base}
 
     def fit(name, x, acc):
@@ -678,14 +668,496 @@ def tune_step_sizes(sampler: GPUSampler, n_burn: int, n_levels: int,
             new[name][0, j] = fit(name, logs[name][:, 0, j], acc)
     acc = np.array([c["lamWOs"][0] for c in counts])
     new["lamWOs"][0, 0] = fit("lamWOs", logs["lamWOs"][:, 0, 0], acc)
+    info = {"scales": 2.0 ** ex, "trials": n_burn, "base": base, "new": new,
+            "accepts": {
+                "betaU": np.array([[c[("betaU", k)] for k in range(d + 1)] for c in counts]),
+                "lamUz": np.array([c["lamUz"] for c in counts]),
+                "lamWs": np.array([c["lamWs"] for c in counts]),
+                "lamWOs": np.array([c["lamWOs"] for c in counts])}}
+    return new, info
+
+
+def tune_step_sizes(sampler: GPUSampler, n_burn: int, n_levels: int,
+                    rng: np.random.Generator) -> None:
+    """GPMSA-style step-size tuning (see module doc); updates params' mcmcStepParam in place
+    and leaves the sampler's chain at the state reached."""
+    pr = sampler.params
+    if sampler.st is None:
+        sampler.init_state()
+    ex = _ladder(n_levels)
+    base = {k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
+    # burn-in at the default steps first: acceptance counted while the chain is still
+    # travelling from the start values would make the smallest-step level look worst
+    sampler.set_steps(1.0)
+    sampler.run(n_burn, rng, record=False)
+    counts = []
+    for e in ex:
+        sampler.set_steps(2.0 ** e)
+        sampler.reset_counts()
+        sampler.run(n_burn, rng, record=False)
+        counts.append(sampler.counts())
+    new, info = _fit_chain_steps(pr, base, ex, counts, n_burn)
     for k in base:
         getattr(pr, k).mcmcStepParam = new[k]
     sampler.set_steps(1.0)
     sampler.reset_counts()
-    sampler.last_tune = {"scales": 2.0 ** ex, "trials": n_burn, "base": base, "new": new,
-                         "accepts": {
-                             "betaU": np.array([[c[("betaU", k)] for k in range(d + 1)]
-                                                for c in counts]),
-                             "lamUz": np.array([c["lamUz"] for c in counts]),
-                             "lamWs": np.array([c["lamWs"] for c in counts]),
-                             "lamWOs": np.array([c["lamWOs"] for c in counts])}}
+    sampler.last_tune = info
+
+
+# ------------------------------------------------------------------------ ensemble sampler
+_SHARED_FIELDS = ("val_shape", "dist", "params", "bounds", "mcmcStepType")
+
+
+def check_shared_priors(params: list) -> None:
+    """Raise ValueError naming the first field in which a ModelParams of the list differs from
+    the first one: an ensemble shares d and P (val_shape), the prior families and parameters,
+    the bounds and the step types; values and step sizes are per chain."""
+    for c, pr in enumerate(params[1:], start=1):
+        for nm in ModelParams.names:
+            for f in _SHARED_FIELDS:
+                a, b = getattr(getattr(params[0], nm), f), getattr(getattr(pr, nm), f)
+                if (a if isinstance(a, str) else tuple(a)) != (b if isinstance(b, str)
+                                                               else tuple(b)):
+                    raise ValueError(f"ensemble: model {c} differs from model 0 in {nm}.{f} "
+                                     f"({b!r} != {a!r})")
+
+
+def loglik_max_batch(n: int, dev: torch.device) -> int | None:
+    """Largest gp_loglik batch at order n that the persistent factorisation takes on the current
+    stream of ``dev`` (gp_pp_plan_stream: GP_PP_PLAN_ELIGIBLE), or None when n itself is beyond
+    its range (every batch then takes the blocked path, so there is nothing to stay within).  A
+    larger batch silently takes the blocked sweep + L^-1 path: much slower, and equal to the
+    in-chain path only to 1e-11."""
+    out = (ctypes.c_longlong * len(_capi.PP_PLAN))()
+    stream = kernels._stream(dev)
+
+    def plan(batch):
+        rc = _capi.lib().gp_pp_plan_stream(n, batch, 0, -1, out, stream)
+        if rc:
+            raise _capi.GPFitError("gp_pp_plan_stream", rc)
+        return dict(zip(_capi.PP_PLAN, out))
+
+    first = plan(1)
+    if not first["eligible"]:
+        return None
+    # the chains hold one workgroup per problem and need as many workers again
+    best = max(1, int(first["resident"]) // 2)
+    while best > 1 and not plan(best)["eligible"]:
+        best -= 1
+    return best
+
+
+class EnsembleSampler:
+    """C chains stepped together: one gp_mcmc_ens_* launch of C workgroups around each batched
+    gp_loglik of all chains' state sets, instead of C GPUSamplers one after another.
+
+    The chains share X (n, d), P, the prior families / parameters / bounds and the step types;
+    each has its own PC weights ``w_hat[c]`` (P, n), ``LamSim[c]`` (P,), state, step sizes,
+    counters and uniforms (``params[c]``: a ModelParams holding chain c's values and steps).  C
+    repeat chains of one model and C scalar models on one design are the same thing with equal
+    or different ``w_hat``.  Chain c is the Markov chain a lone GPUSampler produces from the same
+    generator: the kernels run GPUSampler's code per chain (csrc/mcmc.hip), and a likelihood
+    does not depend on the batch it is evaluated in.
+
+    Fused sweep only, on a HIP device.  The batch is chain-major, and gp_loglik is issued in
+    slices of whole chains of at most ``max_batch`` problems: by default the largest batch the
+    persistent factorisation takes (loglik_max_batch; beyond it gp_loglik falls back to a much
+    slower path).  The default group size starts from default_spec(n, C P, d + 3) and is lowered
+    while one chain's (2^spec - 1) P problems exceed ``max_batch``.  Slices of equal size share
+    one workspace (the workspace's layout depends on its batch, so sizes cannot share).
+    """
+
+    def __init__(self, X: torch.Tensor, w_hat: torch.Tensor, LamSim: torch.Tensor, params: list,
+                 use_graph: bool | None = None, spec: int | None = None,
+                 max_batch: int | None = None):
+        self.X = X.contiguous()
+        self.dev = self.X.device
+        if self.dev.type != "cuda":
+            raise ValueError("EnsembleSampler runs the fused sweep: it needs a HIP device")
+        self.w = w_hat.to(self.dev, F64).contiguous()                   # (C, P, n)
+        if self.w.dim() != 3:
+            raise ValueError("w_hat must be (C, P, n)")
+        self.C, self.P, self.n = self.w.shape
+        self.d = self.X.shape[1]
+        params = list(params)
+        if len(params) != self.C:
+            raise ValueError(f"{len(params)} ModelParams for {self.C} chains")
+        if not 1 <= self.C <= _capi.MCMC_MAX_CHAINS:
+            raise ValueError(f"1 .. {_capi.MCMC_MAX_CHAINS} chains (GPFIT_MCMC_MAX_CHAINS)")
+        check_shared_priors(params)
+        if params[0].betaU.val_shape != (self.d + 1, self.P):
+            raise ValueError(f"params are for (d, P) = ({params[0].betaU.val_shape[0] - 1}, "
+                             f"{params[0].betaU.val_shape[1]}), the data for ({self.d}, {self.P})")
+        if self.X.shape[0] != self.n:
+            raise ValueError("X and w_hat disagree on n")
+        self.params = params
+        C, P, d = self.C, self.P, self.d
+        self.lam = LamSim.to(self.dev, F64).reshape(C, P).contiguous()
+        self.nu = uniforms_per_sweep(d, P)
+        self.u = torch.zeros((C, self.nu), dtype=F64, device=self.dev)
+        self.steps = {k: torch.zeros((C,) + getattr(params[0], k).val_shape, dtype=F64,
+                                     device=self.dev) for k in ModelParams.names}
+        self.set_steps(1.0)
+        # the recorded state, one flat row per chain, laid out as GPUSampler's
+        self._cols = {"betaU": (0, (d + 1) * P)}
+        o = (d + 1) * P
+        for k, w_ in (("lamUz", P), ("lamWs", P), ("lamWOs", 1), ("logPost", 1)):
+            self._cols[k] = (o, o + w_)
+            o += w_
+        self._flat = torch.zeros((C, o), dtype=F64, device=self.dev)
+        self._ll = torch.zeros((C, P), dtype=F64, device=self.dev)
+        self._acc = torch.zeros((C, d + 4, P), dtype=F64, device=self.dev)
+        self._scratch = torch.zeros((C, 3 * _capi.MCMC_MAX_GROUP * P), dtype=F64,
+                                    device=self.dev)
+        self.st = None
+        if use_graph is None:
+            use_graph = os.environ.get("GPFIT_MCMC_GRAPH", "1") == "1"
+        self.use_graph = bool(use_graph)
+        self.graph = None
+        self.block = max(1, int(os.environ.get("GPFIT_MCMC_BLOCK", "16")))
+        self._merge = os.environ.get("GPFIT_MCMC_MERGE", "1") == "1"
+        self._bgraph = {}
+        # slices of whole chains within the persistent factorisation's range
+        limit = loglik_max_batch(self.n, self.dev) if max_batch is None else int(max_batch)
+        self.max_batch = C * (2 ** _capi.MCMC_MAX_GROUP - 1) * P if limit is None else limit
+        if P > self.max_batch:
+            raise ValueError(f"one chain's {P} GPs do not fit a gp_loglik batch of at most "
+                             f"{self.max_batch} problems (max_batch; by default the persistent "
+                             "factorisation's range on this stream)")
+        given = spec if spec is not None else int(os.environ.get("GPFIT_MCMC_SPEC", "0"))
+        if given:
+            if not 1 <= given <= _capi.MCMC_MAX_GROUP:
+                raise ValueError(f"spec must be 1 .. {_capi.MCMC_MAX_GROUP}")
+            if (2 ** given - 1) * P > self.max_batch:
+                raise ValueError(f"spec {given}: one chain's {(2 ** given - 1) * P} problems "
+                                 f"exceed the gp_loglik batch limit {self.max_batch}")
+            spec = given
+        else:
+            spec = default_spec(self.n, C * P, d + 3)
+            while (2 ** spec - 1) * P > self.max_batch:
+                spec -= 1
+        self.spec = spec
+        codes = list(range(1, d + 4))
+        self.groups = [codes[i:i + spec] for i in range(0, len(codes), spec)]
+        self._ws = {}
+        self._gbuf = {}
+        for sets in {1} | {2 ** len(g) - 1 for g in self.groups}:   # 1: init_state's call
+            R = sets * P
+            self._gbuf[sets] = dict(
+                chunk=max(1, self.max_batch // R),
+                beta=torch.empty((C * R, d), dtype=F64, device=self.dev),
+                s=torch.empty(C * R, dtype=F64, device=self.dev),
+                delta=torch.empty(C * R, dtype=F64, device=self.dev),
+                ll=torch.empty(C * R, dtype=F64, device=self.dev),
+                w=self.w[:, None].expand(C, sets, P, self.n).reshape(C * R, self.n).contiguous())
+            for c0 in range(0, C, self._gbuf[sets]["chunk"]):
+                B = (min(C, c0 + self._gbuf[sets]["chunk"]) - c0) * R
+                if B not in self._ws:
+                    self._ws[B] = kernels.LoglikWorkspace(self.n, B, self.dev)
+        T = self._T = _capi.McmcStrides()
+        T.betaU = T.lamUz = T.lamWs = T.lamWOs = T.lp = self._flat.shape[1]
+        T.ll, T.lam, T.u, T.acc, T.scratch = P, P, self.nu, (d + 4) * P, self._scratch.shape[1]
+        T.step_betaU, T.step_lamUz, T.step_lamWs, T.step_lamWOs = (d + 1) * P, P, P, 1
+        self._kinds = [(ctypes.c_int * len(g))(*g) for g in self.groups]
+
+    def _t(self, a) -> torch.Tensor:
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.dev)
+
+    def _view(self, name: str) -> torch.Tensor:
+        a, b = self._cols[name]
+        return self._flat[:, a:b]
+
+    # -- state (per chain) ---------------------------------------------------------------
+    def init_state(self) -> None:
+        """Every chain's state from its params' current values, ll from one sliced gp_loglik."""
+        C, P, d = self.C, self.P, self.d
+        for k in ModelParams.names:
+            self._view(k).copy_(self._t(np.stack([getattr(pr, k).val.reshape(-1)
+                                                  for pr in self.params])))
+        buf = self._gbuf[1]
+        betaU = self._view("betaU").reshape(C, d + 1, P)
+        buf["beta"].view(C, P, d).copy_(betaU[:, 1:].transpose(1, 2))
+        torch.reciprocal(self._view("lamUz"), out=buf["s"].view(C, P))
+        torch.add(torch.reciprocal(self._view("lamWs")),
+                  torch.reciprocal(self._view("lamWOs") * self.lam), out=buf["delta"].view(C, P))
+        self._loglik(1)
+        self._ll.copy_(buf["ll"].view(C, P))
+        self.st = self._flat                    # the states: one flat row per chain
+        self.reset_counts()
+
+    def reset_counts(self) -> None:
+        self._acc.zero_()
+
+    def counts(self) -> list:
+        """Per chain, GPUSampler.counts()'s dict."""
+        a, d = self._acc.cpu().numpy(), self.d
+        out = []
+        for c in range(self.C):
+            cnt = {("betaU", k): a[c, k].copy() for k in range(d + 1)}
+            cnt.update({"lamUz": a[c, d + 1].copy(), "lamWs": a[c, d + 2].copy(),
+                        "lamWOs": a[c, d + 3, :1].copy()})
+            out.append(cnt)
+        return out
+
+    def set_steps(self, scale: float = 1.0) -> None:
+        for k in ModelParams.names:
+            self.steps[k].copy_(self._t(np.stack([getattr(pr, k).mcmcStepParam * scale
+                                                  for pr in self.params])))
+
+    def write_back(self) -> None:
+        flat = self._flat.cpu().numpy()
+        for c, pr in enumerate(self.params):
+            for k in ModelParams.names:
+                a, b = self._cols[k]
+                p = getattr(pr, k)
+                p.val = flat[c, a:b].reshape(p.val_shape).copy()
+
+    # -- one sweep -----------------------------------------------------------------------
+    def _loglik(self, sets: int) -> None:
+        """gp_loglik over the chain-major batch of ``sets`` state sets per chain, in slices of
+        whole chains."""
+        buf, R = self._gbuf[sets], sets * self.P
+        for c0 in range(0, self.C, buf["chunk"]):
+            r0, r1 = c0 * R, min(self.C, c0 + buf["chunk"]) * R
+            kernels.loglik(self.X, buf["beta"][r0:r1], buf["s"][r0:r1], buf["delta"][r0:r1],
+                           buf["w"][r0:r1], self._ws[r1 - r0], out=buf["ll"][r0:r1])
+
+    def _state_struct(self) -> "_capi.McmcState":
+        """gp_mcmc_state of chain 0 over the static buffers (self._T: the strides)."""
+        pr = self.params[0]
+        S = _capi.McmcState()
+        for nm, t in (("betaU", self._view("betaU")), ("lamUz", self._view("lamUz")),
+                      ("lamWs", self._view("lamWs")), ("lamWOs", self._view("lamWOs")),
+                      ("ll", self._ll), ("lam", self.lam), ("u", self.u),
+                      ("step_betaU", self.steps["betaU"]), ("step_lamUz", self.steps["lamUz"]),
+                      ("step_lamWs", self.steps["lamWs"]), ("step_lamWOs", self.steps["lamWOs"]),
+                      ("acc", self._acc), ("lp", self._view("logPost")),
+                      ("scratch", self._scratch)):
+            if t.dtype != F64:
+                raise TypeError(f"mcmc state buffer {nm} must be float64")
+            setattr(S, nm, t.data_ptr())
+        if not self.u.is_contiguous() or self.u.shape != (self.C, self.nu):
+            raise TypeError("uniforms must be a contiguous (C, nu) block")
+        S.P, S.d = self.P, self.d
+        for i, nm in enumerate(ModelParams.names):
+            p = getattr(pr, nm)
+            S.dist[i] = _capi.MCMC_DIST[p.dist]
+            S.steptype[i] = _capi.MCMC_STEP[p.mcmcStepType]
+            S.pa[i], S.pb[i] = p.params
+            S.lo[i], S.hi[i] = p.bounds
+        return S
+
+    def _sweep(self) -> None:
+        """GPUSampler._sweep_fused with the gp_mcmc_ens_* calls and the sliced gp_loglik."""
+        self._S = self._state_struct()          # kept alive: the library reads it per call
+        S, T, C = ctypes.addressof(self._S), ctypes.addressof(self._T), self.C
+        stream = kernels._stream(self.dev)
+        last = len(self.groups) - 1
+        kinds = [ctypes.addressof(k) for k in self._kinds]
+        bufs = [self._gbuf[2 ** len(g) - 1] for g in self.groups]
+
+        def outs(b):
+            return b["beta"].data_ptr(), b["s"].data_ptr(), b["delta"].data_ptr()
+
+        _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[0], len(self.groups[0]), 1,
+                   *outs(bufs[0]), stream)
+        for gi, grp in enumerate(self.groups):
+            self._loglik(2 ** len(grp) - 1)
+            ll = bufs[gi]["ll"].data_ptr()
+            if gi == last or not self._merge:
+                _capi.call("gp_mcmc_ens_decide", S, T, C, kinds[gi], len(grp), int(gi == last),
+                           ll, stream)
+                if gi < last:
+                    _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[gi + 1],
+                               len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]), stream)
+            else:
+                _capi.call("gp_mcmc_ens_step", S, T, C, kinds[gi], len(grp), 0, ll, S,
+                           kinds[gi + 1], len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]),
+                           stream)
+
+    def _capture(self) -> None:
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._sweep()
+        self.graph = g
+
+    def sweep(self) -> None:
+        if self.use_graph:
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+        else:
+            self._sweep()
+
+    def _capture_block(self, record: bool) -> None:
+        """``block`` sweeps as one graph (GPUSampler._capture_block): sweep j reads the (C, nu)
+        uniforms of block row j and copies the flat states into record row j."""
+        B = self.block
+        if not hasattr(self, "_ublk"):
+            self._ublk = torch.zeros((B, self.C, self.nu), dtype=F64, device=self.dev)
+            self._rblk = torch.zeros((B,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        u0 = self.u
+        try:
+            with torch.cuda.graph(g):
+                for j in range(B):
+                    self.u = self._ublk[j]
+                    self._sweep()
+                    if record:
+                        self._rblk[j].copy_(self._flat)
+        finally:
+            self.u = u0
+        self._bgraph[record] = g
+
+    # -- chains --------------------------------------------------------------------------
+    def run(self, nsamp: int, rngs: list, record: bool = True, block: int = 64):
+        """``nsamp`` sweeps of every chain from the current states; chain c consumes
+        ``rngs[c].random((rows, nu))`` block by block exactly as GPUSampler.run consumes its one
+        generator.  Returns, when ``record``, the samples dict with a leading chain axis: betaU
+        (C, N, (d+1) P), lamUz, lamWs (C, N, P), lamWOs, logPost (C, N, 1)."""
+        if len(rngs) != self.C:
+            raise ValueError(f"{len(rngs)} generators for {self.C} chains")
+        if self.st is None:
+            self.init_state()
+        if record:
+            rec = torch.empty((nsamp,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
+        B = self.block if self.use_graph and self.block > 1 else 0
+        for a in range(0, nsamp, block):
+            b = min(nsamp, a + block)
+            U = self._t(np.stack([r.random((b - a, self.nu)) for r in rngs], axis=1))
+            i = a
+            while B and b - i >= B:                     # whole graph blocks
+                if record not in self._bgraph:
+                    self._capture_block(record)
+                self._ublk.copy_(U[i - a:i - a + B])
+                self._bgraph[record].replay()
+                if record:
+                    rec[i:i + B].copy_(self._rblk)
+                i += B
+            for i in range(i, b):                       # the rest one sweep at a time
+                self.u.copy_(U[i - a])
+                self.sweep()
+                if record:
+                    rec[i].copy_(self._flat)
+        for ws in self._ws.values():                    # one host check per run
+            ws.check_status()
+        if not record:
+            return None
+        rec = rec.cpu().numpy().transpose(1, 0, 2)
+        return {k: rec[:, :, a:b].copy() for k, (a, b) in self._cols.items()}
+
+
+def tune_step_sizes_ensemble(sampler: EnsembleSampler, n_burn: int, n_levels: int,
+                             rngs: list) -> None:
+    """tune_step_sizes over a whole ensemble: the same burn-in and ladder, every chain stepped
+    together, then the same per-element logistic fits per chain.  Updates each params[c]'s
+    mcmcStepParam, leaves the chains at the states reached, and sets ``sampler.last_tune`` to the
+    list of per-chain records."""
+    if sampler.st is None:
+        sampler.init_state()
+    ex = _ladder(n_levels)
+    bases = [{k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
+             for pr in sampler.params]
+    sampler.set_steps(1.0)
+    sampler.run(n_burn, rngs, record=False)
+    counts = []
+    for e in ex:
+        sampler.set_steps(2.0 ** e)
+        sampler.reset_counts()
+        sampler.run(n_burn, rngs, record=False)
+        counts.append(sampler.counts())
+    sampler.last_tune = []
+    for c, pr in enumerate(sampler.params):
+        new, info = _fit_chain_steps(pr, bases[c], ex, [lev[c] for lev in counts], n_burn)
+        for k in new:
+            getattr(pr, k).mcmcStepParam = new[k]
+        sampler.last_tune.append(info)
+    sampler.set_steps(1.0)
+    sampler.reset_counts()
+
+
+# ------------------------------------------------------------------ convergence diagnostics
+def _draws(chains, nburn: int) -> np.ndarray:
+    x = np.asarray(chains, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3:
+        raise ValueError("chains must be (C, N) or (C, N, K)")
+    return x[:, int(nburn):]
+
+
+def rhat(chains, nburn: int = 0) -> np.ndarray:
+    """Split-R-hat per parameter element (Gelman et al. 2013, Bayesian Data Analysis 3rd ed.,
+    section 11.4).  ``chains`` is (C, N, K) (or (C, N)); the first ``nburn`` draws are dropped,
+    leaving N' per chain.  With h = N' // 2 each chain gives two sequences, its first h and its
+    last h draws (the middle draw of an odd N' is unused): m = 2 C sequences x_j of length h, with
+    means xbar_j, grand mean xbar and variances s_j^2 (divisor h - 1).  Then::
+
+        B = h / (m - 1) sum_j (xbar_j - xbar)^2        W = 1/m sum_j s_j^2
+        var+ = (h - 1) / h W + B / h                   R-hat = sqrt(var+ / W)
+
+    Returns (K,) (a scalar array for (C, N)); NaN where W = 0 (a constant chain) or h < 2."""
+    x = _draws(chains, nburn)
+    C, N, K = x.shape
+    h = N // 2
+    if h < 2:
+        return np.full(np.shape(chains)[2:], np.nan)
+    seq = np.concatenate([x[:, :h], x[:, N - h:]], axis=0)              # (2 C, h, K)
+    m = seq.shape[0]
+    means = seq.mean(axis=1)
+    B = h / (m - 1.0) * ((means - means.mean(axis=0)) ** 2).sum(axis=0)
+    W = seq.var(axis=1, ddof=1).mean(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = np.sqrt(((h - 1.0) / h * W + B / h) / W)
+    return out.reshape(np.shape(chains)[2:])
+
+
+def _autocov_fft(x: np.ndarray) -> np.ndarray:
+    """Biased autocovariance along axis 1 of (C, N, K): a[c, t] = 1/N sum_{i < N - t}
+    (x[c, i] - xbar_c)(x[c, i + t] - xbar_c), by FFT of the zero-padded centred series."""
+    N = x.shape[1]
+    z = x - x.mean(axis=1, keepdims=True)
+    f = np.fft.rfft(z, n=2 * N, axis=1)
+    return np.fft.irfft(f * np.conj(f), n=2 * N, axis=1)[:, :N] / N
+
+
+def ess(chains, nburn: int = 0) -> np.ndarray:
+    """Effective sample size per parameter element.  ``chains`` is (C, N, K) (or (C, N)); after
+    dropping ``nburn`` draws, per chain c: mean xbar_c and the biased autocovariance
+    a_c(t) = 1/N sum_{i=1}^{N-t} (x_{c,i} - xbar_c)(x_{c,i+t} - xbar_c) (computed by FFT).  With::
+
+        W = N / (N - 1) mean_c a_c(0)
+        var+ = (N - 1) / N W + var_c(xbar_c)           (divisor C - 1; 0 for C = 1)
+        rho_0 = 1,   rho_t = 1 - (W - mean_c a_c(t)) / var+      (t = 1 .. N - 1)
+
+    (the chain-averaged autocorrelations of Gelman et al. 2013, eq. 11.7, in autocovariance
+    form), the sum is cut by Geyer's (1992) initial positive sequence: P_k = rho_2k + rho_2k+1,
+    k = 0 .. (N // 2) - 1; K = the first k >= 1 with P_k <= 0 (all pairs if none is)::
+
+        tau = -1 + 2 sum_{k < K} P_k                   ESS = C N / tau
+
+    Returns (K,) (a scalar array for (C, N)); NaN where var+ = 0 (a constant chain) or N < 4."""
+    x = _draws(chains, nburn)
+    C, N, K = x.shape
+    shape = np.shape(chains)[2:]
+    if N < 4:
+        return np.full(shape, np.nan)
+    acov = _autocov_fft(x)                                              # (C, N, K)
+    W = N / (N - 1.0) * acov[:, 0].mean(axis=0)
+    between = x.mean(axis=1).var(axis=0, ddof=1) if C > 1 else np.zeros(K)
+    varp = (N - 1.0) / N * W + between
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = 1.0 - (W[None] - acov.mean(axis=0)) / varp[None]          # (N, K)
+    rho[0] = 1.0
+    npair = N // 2
+    pairs = rho[0:2 * npair:2] + rho[1:2 * npair:2]                     # (npair, K)
+    out = np.full(K, np.nan)
+    for e in range(K):
+        if not varp[e] > 0:
+            continue
+        stop = np.flatnonzero(pairs[1:, e] <= 0)
+        kk = stop[0] + 1 if stop.size else npair
+        out[e] = C * N / (-1.0 + 2.0 * pairs[:kk, e].sum())
+    return out.reshape(shape)

@@ -23,6 +23,7 @@ import torch
 from . import blas
 from .blas import CM, gemm
 from .emulator import EmulatorData, EmulatorModel
+from .emulator import fit_ensemble  # noqa: F401  (several models on one design, fitted together)
 from .mcmc import SepiaParam
 from .svd import LegacyNormalDraw, randomized_svd
 

@@ -420,6 +420,58 @@ int gp_mcmc_group_step(const gp_mcmc_state* S, const int* kinds, int g, int last
                        hipStream_t stream);
 
 /*
+ * The same three steps for an ensemble of `nchains` chains that share X, P, d, the priors, the
+ * bounds and the step types (C repeat chains of one model, or C models on one design: equal or
+ * different w_hat behind gp_loglik).  S describes chain 0; `strides` holds, for each pointer
+ * field of gp_mcmc_state, the distance in doubles from one chain's buffer to the next chain's.
+ * Workgroup c runs gp_mcmc_group_*'s code on chain c's buffers: the same arithmetic in the same
+ * order (no FMA contraction, the in-order sums of lamWOs' decision and of lp), no atomics, and
+ * it touches no other chain's memory, so a chain's results do not depend on the other chains of
+ * the call, and nchains = 1 gives gp_mcmc_group_*'s bits whatever the strides hold.
+ * The batch is chain-major: chain c's rows of beta / s / delta / ll_all start at row
+ * c (2^g - 1) P and are laid out within the chain as above, so any run of whole chains is one
+ * contiguous gp_loglik batch (gp_mcmc_ens_step: ll_all with the decided group's g, beta / s /
+ * delta with the next group's).
+ * Strides: 0 = every chain reads the same buffer, allowed for the buffers the kernels never
+ * write (lam, u, step_betaU, step_lamUz, step_lamWs, step_lamWOs; any stride >= 0 is accepted
+ * for them).  For a written buffer the stride must be at least its per-chain extent: betaU
+ * (d+1) P, lamUz, lamWs, ll P, lamWOs, lp 1, acc (d+4) P, scratch 3 GPFIT_MCMC_MAX_GROUP P.
+ * With nchains = 1 the strides are not read (the struct must still be given).
+ * gp_mcmc_ens_step applies the one `strides` to S and to S_next.
+ * nchains <= GPFIT_MCMC_MAX_CHAINS = 4096.  The launch grid would take far more; the limit
+ * keeps the row count of a whole ensemble's batch, nchains (2^GPFIT_MCMC_MAX_GROUP - 1) P <=
+ * 4096 * 15 * 1024 < 2^26, well inside gp_loglik's int `batch`, and is already beyond what one
+ * device factorises at a time (the caller slices the batch by whole chains).
+ * Return codes (argument checks in this order, before any launch):
+ *   gp_mcmc_ens_prep / gp_mcmc_ens_decide
+ *     -1 S null; -2 P outside 1..1024; -3 d outside 1..GPFIT_MAX_DIM; -4 g outside
+ *     1..GPFIT_MCMC_MAX_GROUP or kinds null; -5 a null pointer in S; -6 an update code outside
+ *     1..d+3; -7 beta, s or delta null (prep), ll_all null (decide); -8 nchains outside
+ *     1..GPFIT_MCMC_MAX_CHAINS; -9 strides null, or (nchains > 1) a negative stride or a written
+ *     buffer's stride below its per-chain extent;
+ *   gp_mcmc_ens_step
+ *     -1 .. -6, -7 (ll_all), -8, -9 for the decided group as above; then the next group's prep
+ *     codes - 10: -11 .. -16 for S_next / kinds_next / g_next, -17 beta, s or delta null, -18
+ *     S_next->P != S->P, -19 the strides against S_next's extents.
+ * 0 on success; GPFIT_ERR_HIP - e for a launch error.
+ */
+#define GPFIT_MCMC_MAX_CHAINS 4096
+typedef struct {
+  long long betaU, lamUz, lamWs, lamWOs, ll, lam, u, step_betaU, step_lamUz, step_lamWs,
+      step_lamWOs, acc, lp, scratch;
+} gp_mcmc_strides;
+int gp_mcmc_ens_prep(const gp_mcmc_state* S, const gp_mcmc_strides* strides, int nchains,
+                     const int* kinds, int g, int first, double* beta, double* s, double* delta,
+                     hipStream_t stream);
+int gp_mcmc_ens_decide(const gp_mcmc_state* S, const gp_mcmc_strides* strides, int nchains,
+                       const int* kinds, int g, int last, const double* ll_all,
+                       hipStream_t stream);
+int gp_mcmc_ens_step(const gp_mcmc_state* S, const gp_mcmc_strides* strides, int nchains,
+                     const int* kinds, int g, int last, const double* ll_all,
+                     const gp_mcmc_state* S_next, const int* kinds_next, int g_next, int first,
+                     double* beta, double* s, double* delta, hipStream_t stream);
+
+/*
  * Host-side (no device, no stream): `count` float32 deviates of numpy's legacy global
  * generator exactly as src/svd.py:51 draws randomized_svd's test matrix,
  * np.random.normal(size=...).astype(np.float32) -- MT19937 + the polar Box-Muller method
