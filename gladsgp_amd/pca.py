@@ -34,7 +34,17 @@ class TruncationCurve:
     ``sse`` = sum e^2, ``sum`` = sum e, ``rmse`` = sqrt(sse / (n ny)) (the reference's Frobenius
     RMSE), ``var`` = np.var(e) = sse / N - (sum / N)^2, ``node_rmse`` (R, ny) = sqrt(sum_i e^2 / n)
     when asked for.  :func:`truncation_curve` adds the factors it used (``U``, ``S``, ``Vh``) and
-    ``cvar`` = cumsum(S^2) / sum(S^2)."""
+    ``cvar`` = cumsum(S^2) / sum(S^2).
+
+    ``var`` is the one-pass form of the two sums gp_pca_trunc returns, so it cancels when the
+    residual's mean is large against its spread: with A = sse / N, B = sum / N and u = 2^-53 its
+    error is bounded by the two sums' own errors (|dsse| + 2 |B| |dsum|) / N plus
+    u (A + 3 B^2 + |A - B^2|), about u (A + 3 B^2) / (A - B^2) relative -- (B / spread)^2 units in
+    the last place, where a two-pass np.var of the stored residual keeps a few.  Measured on an
+    MI355X with a mean of 1e4 spreads: 2.7e6 times the two-pass error, under 1 % of that bound
+    (tests/_mp_field_ref.py ``one_pass_var_term``).  sse has lost the
+    information by then, so no arithmetic on the two sums restores it; a residual whose mean
+    matters should be centred first (the reference's residuals are: mu is the column mean)."""
 
     ranks: np.ndarray
     sse: object

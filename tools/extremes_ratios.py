@@ -2,12 +2,13 @@
 (regime, n), worst over the entry points that produce it and over the factorisation paths, from
 the helpers of tests/test_gpu_extremes.py; then the same for the PCA front end (statistics,
 eigensolver, randomized SVD, weights) from tests/test_gpu_pca_extremes.py, and for the joint
-covariance, its factor and the joint draws from tests/test_gpu_joint_extremes.py.  Needs a HIP
-device.  Entries above 16 also show, in parentheses, 16 error / bound with the documented term:
-they must be in tests/_mp_ref.FINDINGS, tests/_mp_pca_ref.FINDINGS or
-tests/_mp_joint_ref.FINDINGS_COV.
+covariance, its factor and the joint draws from tests/test_gpu_joint_extremes.py, and for the
+field back end (gp_field, gp_field_summary, gp_field_score, gp_pca_trunc) from
+tests/test_gpu_field_extremes.py.  Needs a HIP device.  Entries above 16 also show, in
+parentheses, 16 error / bound with the documented term: they must be in tests/_mp_ref.FINDINGS,
+tests/_mp_pca_ref.FINDINGS, tests/_mp_joint_ref.FINDINGS_COV or tests/_mp_field_ref.FINDINGS.
 
-    python tools/extremes_ratios.py [chain|pca|joint]
+    python tools/extremes_ratios.py [chain|pca|joint|field]
 """
 import os
 import sys
@@ -142,6 +143,63 @@ def joint(dev):
         print(f"| {m} | " + " | ".join(cells) + " |")
 
 
+def field(dev):
+    """The field back end (tests/test_gpu_field_extremes.py): worst error / noise per (kernel
+    output, regime) over the regime's cases; float32 columns show what is left above half a
+    float32 ulp of the truth."""
+    import _mp_field_ref as F
+    import test_gpu_field_extremes as TF
+
+    def table(title, names, regimes, cells):
+        print(f"\n| {title} | " + " | ".join(names) + " |")
+        print("|---|" + "---|" * len(names))
+        for regime in regimes:
+            print(f"| {regime} | " + " | ".join(cells[regime].get(nm, "-") for nm in names) + " |")
+
+    def put(acc, regime, nm, ratio):
+        acc.setdefault(regime, {})
+        acc[regime][nm] = max(acc[regime].get(nm, 0.0), ratio)
+
+    acc = {}
+    for case in F.FIELD_CASES:
+        for sdmu, err, e64, nz, exc, _, _ in TF.field_errors(dev, case):
+            put(acc, case[0], "field fp64", _worst(e64, nz))
+            put(acc, case[0], "field float32", _worst(exc, nz))
+    for case in F.SUMMARY_CASES:
+        for nm, (e, nz, exc) in TF.summary_errors(dev, case)[0].items():
+            put(acc, case[0], nm, _worst(e, nz))
+            put(acc, case[0], nm + " float32", _worst(exc, nz))
+    for scase in F.SCORE_CASES:
+        er, nr, ec, nc, _, _ = TF.score_errors(dev, scase)
+        regime = F.SUMMARY_CASES[scase[0]][0]
+        sr = [k for k in range(8) if k not in TF.ROW_COUNTS]
+        sc = [k for k in range(4) if k not in TF.COL_COUNTS]
+        put(acc, regime, "score rows", _worst(er[:, sr], nr[:, sr]))
+        put(acc, regime, "score cols", _worst(ec[:, sc], nc[:, sc]))
+    names = ["field fp64", "field float32", "mean", "lo", "hi", "mean float32", "lo float32",
+             "hi float32", "score rows", "score cols"]
+    table("field regime", names, F.FIELD_REGIMES,
+          {r: {nm: fmt(v) for nm, v in acc[r].items()} for r in acc})
+
+    acc, cells = {}, {}
+    names = ["sse", "sum", "node", "rmse", "var"]
+    for case in F.TRUNC_CASES:
+        for nm, (e, nz, lim) in TF.trunc_errors(dev, case).items():
+            put(acc, case[0], nm, _worst(e, nz))
+            if np.any(e > F.MARGIN * nz):
+                put(acc, case[0], nm + " bound", F.MARGIN * _worst(e, lim))
+    for regime, row in acc.items():
+        cells[regime] = {}
+        for nm in names:
+            cell = fmt(row[nm])
+            if nm + " bound" in row:
+                cell += f" ({fmt(row[nm + ' bound'])})"
+                if (nm, regime) not in F.FINDINGS:
+                    cell += " NOT A DOCUMENTED FINDING"
+            cells[regime][nm] = cell
+    table("gp_pca_trunc regime", names, F.TRUNC_REGIMES, cells)
+
+
 def main():
     from gladsgp_amd import kernels  # noqa: F401 (loads libgpfit.so)
     dev = torch.device("cuda:0")
@@ -152,6 +210,8 @@ def main():
         pca(dev)
     if which in ("joint", "all"):
         joint(dev)
+    if which in ("field", "all"):
+        field(dev)
 
 
 if __name__ == "__main__":
