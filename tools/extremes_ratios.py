@@ -4,11 +4,13 @@ the helpers of tests/test_gpu_extremes.py; then the same for the PCA front end (
 eigensolver, randomized SVD, weights) from tests/test_gpu_pca_extremes.py, and for the joint
 covariance, its factor and the joint draws from tests/test_gpu_joint_extremes.py, and for the
 field back end (gp_field, gp_field_summary, gp_field_score, gp_pca_trunc) from
-tests/test_gpu_field_extremes.py.  Needs a HIP device.  Entries above 16 also show, in
+tests/test_gpu_field_extremes.py, and for gp_xval (the chain and the kernel alone, per fold
+plan) from tests/test_gpu_xval_extremes.py.  Needs a HIP device.  Entries above 16 also show, in
 parentheses, 16 error / bound with the documented term: they must be in tests/_mp_ref.FINDINGS,
-tests/_mp_pca_ref.FINDINGS, tests/_mp_joint_ref.FINDINGS_COV or tests/_mp_field_ref.FINDINGS.
+tests/_mp_pca_ref.FINDINGS, tests/_mp_joint_ref.FINDINGS_COV, tests/_mp_field_ref.FINDINGS or
+tests/_mp_xval_ref.FINDINGS.
 
-    python tools/extremes_ratios.py [chain|pca|joint|field]
+    python tools/extremes_ratios.py [chain|pca|joint|field|xval]
 """
 import os
 import sys
@@ -200,6 +202,35 @@ def field(dev):
     table("gp_pca_trunc regime", names, F.TRUNC_REGIMES, cells)
 
 
+def xval(dev):
+    """gp_xval (tests/test_gpu_xval_extremes.py): error / noise per (quantity, regime, n, plan)
+    for the chain and for the kernel alone on the truth's and on the device's L^-1."""
+    import _mp_xval_ref as X
+    import test_gpu_xval_extremes as TX
+    layers = ("chain", "hi", "dev")
+    print("\n| regime | n | plan | " +
+          " | ".join(f"{layer} {q}" for layer in layers for q in X.QUANTITIES) + " |")
+    print("|---|---|---|" + "---|" * (3 * len(layers)))
+    worst = {layer: (0.0, None) for layer in layers}
+    for regime, n, plan in X.REGIME_CASES:
+        res = TX.xval_errors(dev, regime, n, plan)
+        cells = []
+        for layer in layers:
+            for q in X.QUANTITIES:
+                err, nz, lim = res[layer][q]
+                cell = fmt(err / nz)
+                if err / nz > worst[layer][0]:
+                    worst[layer] = (err / nz, (q, regime, n, plan))
+                if err > M.MARGIN * nz:
+                    cell += f" ({fmt(M.MARGIN * err / lim)})"
+                    if layer != "chain" or (q, regime, n, plan) not in X.FINDINGS:
+                        cell += " NOT A DOCUMENTED FINDING"
+                cells.append(cell)
+        print(f"| {regime} | {n} | {plan} | " + " | ".join(cells) + " |", flush=True)
+    for layer in layers:
+        print(f"largest ratio, {layer}: {fmt(worst[layer][0])} at {worst[layer][1]}")
+
+
 def main():
     from gladsgp_amd import kernels  # noqa: F401 (loads libgpfit.so)
     dev = torch.device("cuda:0")
@@ -212,6 +243,8 @@ def main():
         joint(dev)
     if which in ("field", "all"):
         field(dev)
+    if which in ("xval", "all"):
+        xval(dev)
 
 
 if __name__ == "__main__":
