@@ -1,23 +1,24 @@
-// Metropolis sweep steps of the GPU sampler (gladsgp_amd.mcmc.GPUSampler), replacing SEPIA's
-// SepiaModel.do_mcmc / tune_step_sizes sweep as src/model.py:225-235 drives it.
+// Metropolis sweep steps of the GPU samplers (gladsgp_amd.mcmc: GPUSampler, one chain, and
+// EnsembleSampler, many), replacing SEPIA's SepiaModel.do_mcmc / tune_step_sizes sweep as
+// src/model.py:225-235 drives it.
 //
 // A sweep is component-wise Metropolis over mcmcList (betaU row by row, lamUz, lamWs, lamWOs).
 // The sampler takes the likelihood-changing updates in speculative groups of g: ONE batched
 // gp_loglik evaluates update i's proposal at each of the 2^i outcomes of the group's earlier
 // updates (state set 2^i - 1 + pat, pat = bit j set when update j was accepted), and the
-// decisions are then taken in order.  Around each gp_loglik this file puts two single-workgroup
-// kernels (thread j = principal component j):
-//   gp_mcmc_group_prep    proposals of the group's updates (and, for the sweep's first group,
+// decisions are then taken in order.  Around each gp_loglik this file puts two kernels of one
+// workgroup per chain (thread j = principal component j), for chains that share X, P, priors,
+// bounds and step types and have their own buffers, a stride apart:
+//   gp_mcmc_ens_prep      proposals of the group's updates (and, for the sweep's first group,
 //                         the prior-only move of betaU row 0), then the Gram inputs
 //                         (beta, s = 1/lamUz, delta = 1/lamWs + 1/(lamWOs LamSim)) of every
 //                         state set
-//   gp_mcmc_group_decide  the accept / reject decisions in order (per GP; lamWOs once for all
+//   gp_mcmc_ens_decide    the accept / reject decisions in order (per GP; lamWOs once for all
 //                         on the sum), state, per-GP likelihood and acceptance counters in place,
 //                         and for the sweep's last group the log posterior
-//   gp_mcmc_group_step    one group's decide and the next group's prep in one launch
-//   gp_mcmc_ens_prep / _decide / _step   the same three for an ensemble of chains that share
-//                         X, P, priors, bounds and step types (mcmc.EnsembleSampler): one
-//                         workgroup per chain runs the single-chain code on that chain's buffers
+//   gp_mcmc_ens_step      one group's decide and the next group's prep in one launch
+//   gp_mcmc_group_prep / _decide / _step   the same three for one chain: they forward to
+//                         gp_mcmc_ens_* with nchains = 1 (one set of kernels serves both)
 // They replace some 100 elementwise launches per group of the tensor-op form of the same sweep
 // (mcmc.py _sweep_torch, kept as the host-logic reference the CPU tests run).  Arithmetic is
 // op-for-op that form's (no FMA contraction), so the chains agree with it and with the oracle
@@ -61,19 +62,14 @@ GP_DEV double log_prior(const gp_mcmc_state& S, int p, double x) {
   }
 }
 
-// The device buffers of the chain a workgroup runs: gp_mcmc_state's pointers as they are (the
-// single-chain kernels) or moved by chain c's strides (the ensemble kernels).  The bodies below
-// read every pointer from here and P, d and the priors from the launch's gp_mcmc_state.
+// The device buffers of the chain a workgroup runs: gp_mcmc_state's pointers moved by chain c's
+// strides.  The bodies below read every pointer from here and P, d and the priors from the
+// launch's gp_mcmc_state.
 struct ChainPtrs {
   double *betaU, *lamUz, *lamWs, *lamWOs, *ll;
   const double *lam, *u, *step_betaU, *step_lamUz, *step_lamWs, *step_lamWOs;
   double *acc, *lp, *scratch;
 };
-
-GP_DEV ChainPtrs chain_ptrs(const gp_mcmc_state& S) {
-  return {S.betaU, S.lamUz, S.lamWs, S.lamWOs, S.ll, S.lam, S.u, S.step_betaU, S.step_lamUz,
-          S.step_lamWs, S.step_lamWOs, S.acc, S.lp, S.scratch};
-}
 
 GP_DEV ChainPtrs chain_ptrs(const gp_mcmc_state& S, const gp_mcmc_strides& T, long long c) {
   return {S.betaU + c * T.betaU, S.lamUz + c * T.lamUz, S.lamWs + c * T.lamWs,
@@ -264,33 +260,10 @@ GP_DEV void decide_body(const GroupArgs& A, const ChainPtrs& Q,
   }
 }
 
-__global__ __launch_bounds__(1024) void mcmc_prep_kernel(GroupArgs A, double* __restrict__ beta,
-                                                         double* __restrict__ s,
-                                                         double* __restrict__ delta) {
-  prep_body(A, chain_ptrs(A.S), beta, s, delta);
-}
-
-__global__ __launch_bounds__(1024) void mcmc_decide_kernel(GroupArgs A,
-                                                           const double* __restrict__ ll_all) {
-  decide_body(A, chain_ptrs(A.S), ll_all);
-}
-
-// A group's decisions, then the next group's proposals and Gram inputs, in one launch (the
-// barrier orders the decisions' state and scratch reads before the proposals' writes)
-__global__ __launch_bounds__(1024) void mcmc_step_kernel(GroupArgs D,
-                                                         const double* __restrict__ ll_all,
-                                                         GroupArgs A, double* __restrict__ beta,
-                                                         double* __restrict__ s,
-                                                         double* __restrict__ delta) {
-  decide_body(D, chain_ptrs(D.S), ll_all);
-  __syncthreads();
-  prep_body(A, chain_ptrs(A.S), beta, s, delta);
-}
-
-// The ensemble forms: workgroup c runs the same bodies on chain c's buffers (the state's
-// pointers moved by c strides) and on chain c's rows of the chain-major batch, which start at
-// c (2^g - 1) P.  No workgroup reads or writes another chain's memory, so a chain's results do
-// not depend on the others of the launch, and a chain's arithmetic is the single-chain kernels'.
+// The kernels: workgroup c runs the bodies on chain c's buffers (the state's pointers moved by c
+// strides) and on chain c's rows of the chain-major batch, which start at c (2^g - 1) P.  No
+// workgroup reads or writes another chain's memory, so a chain's results do not depend on the
+// others of the launch; a lone chain is the launch of one workgroup.
 GP_DEV long long chain_rows(const GroupArgs& A) {
   return (long long)blockIdx.x * ((1LL << A.g) - 1) * A.S.P;
 }
@@ -308,6 +281,8 @@ __global__ __launch_bounds__(1024) void mcmc_ens_decide_kernel(GroupArgs A, gp_m
   decide_body(A, chain_ptrs(A.S, T, blockIdx.x), ll_all + chain_rows(A));
 }
 
+// A group's decisions, then the next group's proposals and Gram inputs, in one launch (the
+// barrier orders the decisions' state and scratch reads before the proposals' writes)
 __global__ __launch_bounds__(1024) void mcmc_ens_step_kernel(GroupArgs D, gp_mcmc_strides T,
                                                              const double* __restrict__ ll_all,
                                                              GroupArgs A,
@@ -359,79 +334,43 @@ int group_args(const gp_mcmc_state* S, const int* kinds, int g, int flag, GroupA
   return 0;
 }
 
-int block_for(int P) { return (P + 63) / 64 * 64; }
+// One group's argument checks in gpfit.h's order: the group itself (-1 .. -6, group_args), its
+// batch pointers (-7), the chain count (-8), the strides (-9)
+int check_group(const gp_mcmc_state* S, const gp_mcmc_strides* T, int nchains, const int* kinds,
+                int g, int flag, bool batch_ok, GroupArgs& A) {
+  const int rc = group_args(S, kinds, g, flag, A);
+  if (rc) return rc;
+  if (!batch_ok) return -7;
+  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
+  return bad_strides(T, nchains, S->P, S->d) ? -9 : 0;
+}
+
+// one workgroup per chain, a thread per GP rounded up to whole waves
+template <typename Kernel, typename... Args>
+int launch(Kernel kernel, int nchains, int P, hipStream_t stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3(nchains), dim3((P + 63) / 64 * 64), 0, stream, args...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+}
 
 }  // namespace
-
-extern "C" int gp_mcmc_group_prep(const gp_mcmc_state* S, const int* kinds, int g, int first,
-                                  double* beta, double* s, double* delta, hipStream_t stream) {
-  GroupArgs A;
-  const int rc = group_args(S, kinds, g, first, A);
-  if (rc) return rc;
-  if (!beta || !s || !delta) return -7;
-  hipLaunchKernelGGL(mcmc_prep_kernel, dim3(1), dim3(block_for(S->P)), 0, stream, A, beta, s,
-                     delta);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
-}
-
-extern "C" int gp_mcmc_group_step(const gp_mcmc_state* S, const int* kinds, int g, int last,
-                                  const double* ll_all, const gp_mcmc_state* S_next,
-                                  const int* kinds_next, int g_next, int first, double* beta,
-                                  double* s, double* delta, hipStream_t stream) {
-  GroupArgs D, A;
-  int rc = group_args(S, kinds, g, last, D);
-  if (rc) return rc;
-  if (!ll_all) return -7;
-  rc = group_args(S_next, kinds_next, g_next, first, A);
-  if (rc) return rc - 10;
-  if (!beta || !s || !delta) return -17;
-  if (S_next->P != S->P) return -18;
-  hipLaunchKernelGGL(mcmc_step_kernel, dim3(1), dim3(block_for(S->P)), 0, stream, D, ll_all, A,
-                     beta, s, delta);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
-}
-
-extern "C" int gp_mcmc_group_decide(const gp_mcmc_state* S, const int* kinds, int g, int last,
-                                    const double* ll_all, hipStream_t stream) {
-  GroupArgs A;
-  const int rc = group_args(S, kinds, g, last, A);
-  if (rc) return rc;
-  if (!ll_all) return -7;
-  hipLaunchKernelGGL(mcmc_decide_kernel, dim3(1), dim3(block_for(S->P)), 0, stream, A, ll_all);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
-}
 
 extern "C" int gp_mcmc_ens_prep(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
                                 int nchains, const int* kinds, int g, int first, double* beta,
                                 double* s, double* delta, hipStream_t stream) {
   GroupArgs A;
-  const int rc = group_args(S, kinds, g, first, A);
+  const int rc = check_group(S, strides, nchains, kinds, g, first, beta && s && delta, A);
   if (rc) return rc;
-  if (!beta || !s || !delta) return -7;
-  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
-  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
-  hipLaunchKernelGGL(mcmc_ens_prep_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, A,
-                     *strides, beta, s, delta);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  return launch(mcmc_ens_prep_kernel, nchains, S->P, stream, A, *strides, beta, s, delta);
 }
 
 extern "C" int gp_mcmc_ens_decide(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
                                   int nchains, const int* kinds, int g, int last,
                                   const double* ll_all, hipStream_t stream) {
   GroupArgs A;
-  const int rc = group_args(S, kinds, g, last, A);
+  const int rc = check_group(S, strides, nchains, kinds, g, last, ll_all != nullptr, A);
   if (rc) return rc;
-  if (!ll_all) return -7;
-  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
-  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
-  hipLaunchKernelGGL(mcmc_ens_decide_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, A,
-                     *strides, ll_all);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  return launch(mcmc_ens_decide_kernel, nchains, S->P, stream, A, *strides, ll_all);
 }
 
 extern "C" int gp_mcmc_ens_step(const gp_mcmc_state* S, const gp_mcmc_strides* strides,
@@ -440,18 +379,36 @@ extern "C" int gp_mcmc_ens_step(const gp_mcmc_state* S, const gp_mcmc_strides* s
                                 const int* kinds_next, int g_next, int first, double* beta,
                                 double* s, double* delta, hipStream_t stream) {
   GroupArgs D, A;
-  int rc = group_args(S, kinds, g, last, D);
+  int rc = check_group(S, strides, nchains, kinds, g, last, ll_all != nullptr, D);
   if (rc) return rc;
-  if (!ll_all) return -7;
-  if (nchains < 1 || nchains > GPFIT_MCMC_MAX_CHAINS) return -8;
-  if (bad_strides(strides, nchains, S->P, S->d)) return -9;
   rc = group_args(S_next, kinds_next, g_next, first, A);
   if (rc) return rc - 10;
   if (!beta || !s || !delta) return -17;
   if (S_next->P != S->P) return -18;
   if (bad_strides(strides, nchains, S_next->P, S_next->d)) return -19;
-  hipLaunchKernelGGL(mcmc_ens_step_kernel, dim3(nchains), dim3(block_for(S->P)), 0, stream, D,
-                     *strides, ll_all, A, beta, s, delta);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  return launch(mcmc_ens_step_kernel, nchains, S->P, stream, D, *strides, ll_all, A, beta, s,
+                delta);
+}
+
+// The single-chain entry points: the ensemble's with one chain and strides that are never read
+// (-8, -9 and -19 cannot fire: bad_strides accepts any struct for one chain).
+extern "C" int gp_mcmc_group_prep(const gp_mcmc_state* S, const int* kinds, int g, int first,
+                                  double* beta, double* s, double* delta, hipStream_t stream) {
+  const gp_mcmc_strides none = {};
+  return gp_mcmc_ens_prep(S, &none, 1, kinds, g, first, beta, s, delta, stream);
+}
+
+extern "C" int gp_mcmc_group_decide(const gp_mcmc_state* S, const int* kinds, int g, int last,
+                                    const double* ll_all, hipStream_t stream) {
+  const gp_mcmc_strides none = {};
+  return gp_mcmc_ens_decide(S, &none, 1, kinds, g, last, ll_all, stream);
+}
+
+extern "C" int gp_mcmc_group_step(const gp_mcmc_state* S, const int* kinds, int g, int last,
+                                  const double* ll_all, const gp_mcmc_state* S_next,
+                                  const int* kinds_next, int g_next, int first, double* beta,
+                                  double* s, double* delta, hipStream_t stream) {
+  const gp_mcmc_strides none = {};
+  return gp_mcmc_ens_step(S, &none, 1, kinds, g, last, ll_all, S_next, kinds_next, g_next, first,
+                          beta, s, delta, stream);
 }

@@ -194,8 +194,297 @@ def default_spec(n: int, P: int, updates: int) -> int:
     return min(range(1, _capi.MCMC_MAX_GROUP + 1), key=sweep)
 
 
-class GPUSampler:
-    """Component-wise Metropolis over the P PC-GPs of one emulator, all state on the device.
+class _ChainSweeps:
+    """What GPUSampler (one chain) and EnsembleSampler (many) share: C chains on one design
+    X (n, d), each with its own PC weights ``w[c]`` (P, n), ``lam[c]`` (P,), state, step sizes,
+    counters and uniforms (``params[c]``: a ModelParams holding chain c's values and steps), all
+    in static device buffers with a leading chain axis, and the fused sweep over them: one
+    gp_mcmc_ens_* launch of C workgroups around each batched gp_loglik of all chains' state sets
+    (csrc/mcmc.hip), run eagerly, as a replayed HIP graph of one sweep, or in graphs of
+    ``block`` sweeps.
+
+    The batch is chain-major, and gp_loglik is issued in slices of whole chains of at most
+    ``max_batch`` problems (None: all chains in one call).  Slices of equal size share one
+    workspace (the workspace's layout depends on its batch, so sizes cannot share).  A chain's
+    results do not depend on the others: the kernels touch one chain's memory per workgroup, and a
+    likelihood does not depend on the batch it is evaluated in.
+    """
+
+    def __init__(self, X: torch.Tensor, w: torch.Tensor, lam: torch.Tensor, params: list,
+                 use_graph: bool | None, spec: int, fused: bool, max_batch: int | None):
+        self.X = X.contiguous()
+        self.dev = self.X.device
+        self.C, self.P, self.n = w.shape                                # w: (C, P, n)
+        self.d = self.X.shape[1]
+        self._params = params
+        C, P, d = self.C, self.P, self.d
+        self.lam = lam.to(self.dev, F64).reshape(C, P).contiguous()
+        self.nu = uniforms_per_sweep(d, P)
+        self.u = torch.zeros((C, self.nu), dtype=F64, device=self.dev)   # static uniforms
+        self.steps = {k: torch.zeros((C,) + getattr(params[0], k).val_shape, dtype=F64,
+                                     device=self.dev) for k in ModelParams.names}
+        self.set_steps(1.0)
+        # the recorded state, one flat row per chain: betaU (d+1, P) | lamUz | lamWs | lamWOs |
+        # log post (so a sample is recorded with one copy)
+        self._cols = {"betaU": (0, (d + 1) * P)}
+        o = (d + 1) * P
+        for k, w_ in (("lamUz", P), ("lamWs", P), ("lamWOs", 1), ("logPost", 1)):
+            self._cols[k] = (o, o + w_)
+            o += w_
+        self._flat = torch.zeros((C, o), dtype=F64, device=self.dev)
+        self._ll = torch.zeros((C, P), dtype=F64, device=self.dev)      # per-GP log-likelihood
+        # acceptance counters indexed by update code (gp_mcmc_state.acc)
+        self._acc = torch.zeros((C, d + 4, P), dtype=F64, device=self.dev)
+        self._scratch = torch.zeros((C, 3 * _capi.MCMC_MAX_GROUP * P), dtype=F64,
+                                    device=self.dev)
+        self.st = None
+        if use_graph is None:
+            use_graph = os.environ.get("GPFIT_MCMC_GRAPH", "1") == "1"
+        self.use_graph = bool(use_graph) and self.dev.type == "cuda"
+        self.graph = None
+        # sweeps per replayed graph in run() (GPFIT_MCMC_BLOCK; 1: one sweep per replay)
+        self.block = max(1, int(os.environ.get("GPFIT_MCMC_BLOCK", "16")))
+        # decide + next prep in one launch (gp_mcmc_ens_step); GPFIT_MCMC_MERGE=0: two
+        self._merge = os.environ.get("GPFIT_MCMC_MERGE", "1") == "1"
+        self._bgraph = {}
+        self.fused = fused
+        self.spec = spec
+        self.max_batch = max_batch
+        # the likelihood-changing updates of a sweep by update code, in mcmcList order: betaU
+        # rows 1 .. d, lamUz, lamWs, lamWOs (betaU row 0, the dummy x, moves under its prior
+        # alone)
+        codes = list(range(1, d + 4))
+        self.groups = [codes[i:i + spec] for i in range(0, len(codes), spec)]
+        self._ws = {}
+        self._gbuf = {}
+        for sets in {1} | {2 ** len(g) - 1 for g in self.groups}:   # 1: init_state's call
+            R = sets * P
+            self._gbuf[sets] = dict(
+                chunk=C if max_batch is None else max(1, max_batch // R),
+                beta=torch.empty((C * R, d), dtype=F64, device=self.dev),
+                s=torch.empty(C * R, dtype=F64, device=self.dev),
+                delta=torch.empty(C * R, dtype=F64, device=self.dev),
+                ll=torch.empty(C * R, dtype=F64, device=self.dev),
+                w=w[:, None].expand(C, sets, P, self.n).reshape(C * R, self.n).contiguous())
+            for c0 in range(0, C, self._gbuf[sets]["chunk"]):
+                B = (min(C, c0 + self._gbuf[sets]["chunk"]) - c0) * R
+                if B not in self._ws:
+                    self._ws[B] = kernels.LoglikWorkspace(self.n, B, self.dev)
+        T = self._T = _capi.McmcStrides()
+        T.betaU = T.lamUz = T.lamWs = T.lamWOs = T.lp = self._flat.shape[1]
+        T.ll, T.lam, T.u, T.acc, T.scratch = P, P, self.nu, (d + 4) * P, self._scratch.shape[1]
+        T.step_betaU, T.step_lamUz, T.step_lamWs, T.step_lamWOs = (d + 1) * P, P, P, 1
+        self._kinds = [(ctypes.c_int * len(g))(*g) for g in self.groups]
+
+    def _t(self, a) -> torch.Tensor:
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.dev)
+
+    def _view(self, name: str) -> torch.Tensor:
+        a, b = self._cols[name]
+        return self._flat[:, a:b]
+
+    # -- state (per chain) ---------------------------------------------------------------
+    def init_state(self):
+        """Every chain's state from its params' current values, ll from one sliced gp_loglik."""
+        C, P, d = self.C, self.P, self.d
+        for k in ModelParams.names:
+            self._view(k).copy_(self._t(np.stack([getattr(pr, k).val.reshape(-1)
+                                                  for pr in self._params])))
+        buf = self._gbuf[1]
+        betaU = self._view("betaU").reshape(C, d + 1, P)
+        buf["beta"].view(C, P, d).copy_(betaU[:, 1:].transpose(1, 2))
+        torch.reciprocal(self._view("lamUz"), out=buf["s"].view(C, P))
+        torch.add(torch.reciprocal(self._view("lamWs")),
+                  torch.reciprocal(self._view("lamWOs") * self.lam), out=buf["delta"].view(C, P))
+        self._loglik(1)
+        self._ll.copy_(buf["ll"].view(C, P))
+        if self.st is None:
+            self.st = self._flat                # the states: one flat row per chain
+        self.reset_counts()
+
+    def reset_counts(self) -> None:
+        self._acc.zero_()
+
+    def _counts(self) -> list:
+        """Per chain, the acceptance counts by update: ("betaU", row), lamUz, lamWs (P,) and
+        lamWOs (1,)."""
+        a, d = self._acc.cpu().numpy(), self.d
+        out = []
+        for c in range(self.C):
+            cnt = {("betaU", k): a[c, k].copy() for k in range(d + 1)}
+            cnt.update({"lamUz": a[c, d + 1].copy(), "lamWs": a[c, d + 2].copy(),
+                        "lamWOs": a[c, d + 3, :1].copy()})
+            out.append(cnt)
+        return out
+
+    def set_steps(self, scale: float = 1.0) -> None:
+        for k in ModelParams.names:
+            self.steps[k].copy_(self._t(np.stack([getattr(pr, k).mcmcStepParam * scale
+                                                  for pr in self._params])))
+
+    def write_back(self) -> None:
+        flat = self._flat.cpu().numpy()
+        for c, pr in enumerate(self._params):
+            for k in ModelParams.names:
+                a, b = self._cols[k]
+                p = getattr(pr, k)
+                p.val = flat[c, a:b].reshape(p.val_shape).copy()
+
+    # -- one sweep -----------------------------------------------------------------------
+    def _loglik(self, sets: int) -> None:
+        """gp_loglik over the chain-major batch of ``sets`` state sets per chain, in slices of
+        whole chains."""
+        buf, R = self._gbuf[sets], sets * self.P
+        for c0 in range(0, self.C, buf["chunk"]):
+            r0, r1 = c0 * R, min(self.C, c0 + buf["chunk"]) * R
+            kernels.loglik(self.X, buf["beta"][r0:r1], buf["s"][r0:r1], buf["delta"][r0:r1],
+                           buf["w"][r0:r1], self._ws[r1 - r0], out=buf["ll"][r0:r1])
+
+    def _state_struct(self) -> "_capi.McmcState":
+        """gp_mcmc_state of chain 0 over the static buffers and the shared priors (self._T: the
+        strides to the other chains)."""
+        pr = self._params[0]
+        S = _capi.McmcState()
+        for nm, t in (("betaU", self._view("betaU")), ("lamUz", self._view("lamUz")),
+                      ("lamWs", self._view("lamWs")), ("lamWOs", self._view("lamWOs")),
+                      ("ll", self._ll), ("lam", self.lam), ("u", self.u),
+                      ("step_betaU", self.steps["betaU"]), ("step_lamUz", self.steps["lamUz"]),
+                      ("step_lamWs", self.steps["lamWs"]), ("step_lamWOs", self.steps["lamWOs"]),
+                      ("acc", self._acc), ("lp", self._view("logPost")),
+                      ("scratch", self._scratch)):
+            if t.dtype != F64:
+                raise TypeError(f"mcmc state buffer {nm} must be float64")
+            setattr(S, nm, t.data_ptr())
+        if not self.u.is_contiguous() or self.u.shape != (self.C, self.nu):
+            raise TypeError("uniforms must be a contiguous (C, nu) block")
+        S.P, S.d = self.P, self.d
+        for i, nm in enumerate(ModelParams.names):
+            p = getattr(pr, nm)
+            S.dist[i] = _capi.MCMC_DIST[p.dist]
+            S.steptype[i] = _capi.MCMC_STEP[p.mcmcStepType]
+            S.pa[i], S.pb[i] = p.params
+            S.lo[i], S.hi[i] = p.bounds
+        return S
+
+    def _sweep(self) -> None:
+        """One component-wise Metropolis sweep of every chain on the static buffers (graph-
+        capturable: no allocation that outlives it, no host synchronisation, in-place state
+        updates), each speculative group's proposals and decisions in one-workgroup-per-chain
+        kernels around its gp_loglik (csrc/mcmc.hip): the first group's gp_mcmc_ens_prep, then
+        after each gp_loglik one gp_mcmc_ens_step (this group's decisions + the next group's
+        proposals; gp_mcmc_ens_decide after the last), so 2 + gp_loglik's launches per group
+        instead of the ~100 of the tensor-op form (GPUSampler._sweep_torch, which also says what
+        a speculative group is)."""
+        self._S = self._state_struct()          # kept alive: the library reads it per call
+        S, T, C = ctypes.addressof(self._S), ctypes.addressof(self._T), self.C
+        stream = kernels._stream(self.dev)
+        last = len(self.groups) - 1
+        kinds = [ctypes.addressof(k) for k in self._kinds]
+        bufs = [self._gbuf[2 ** len(g) - 1] for g in self.groups]
+
+        def outs(b):
+            return b["beta"].data_ptr(), b["s"].data_ptr(), b["delta"].data_ptr()
+
+        _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[0], len(self.groups[0]), 1,
+                   *outs(bufs[0]), stream)
+        for gi, grp in enumerate(self.groups):
+            self._loglik(2 ** len(grp) - 1)
+            ll = bufs[gi]["ll"].data_ptr()
+            if gi == last or not self._merge:
+                _capi.call("gp_mcmc_ens_decide", S, T, C, kinds[gi], len(grp), int(gi == last),
+                           ll, stream)
+                if gi < last:
+                    _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[gi + 1],
+                               len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]), stream)
+            else:
+                _capi.call("gp_mcmc_ens_step", S, T, C, kinds[gi], len(grp), 0, ll, S,
+                           kinds[gi + 1], len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]),
+                           stream)
+
+    def _capture(self) -> None:
+        """Record one sweep as a graph (capture does not execute it: the chains are untouched)."""
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._sweep()
+        self.graph = g
+
+    def sweep(self) -> None:
+        if self.use_graph:
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+        else:
+            self._sweep()
+
+    def _capture_block(self, record: bool) -> None:
+        """Record ``block`` sweeps as one graph: sweep j reads the (C, nu) uniforms of row j of a
+        static block and (``record``) copies the flat states into row j of a static record block.
+        One replay per block instead of one per sweep, and one copy per recorded sample instead of
+        one uniform upload + five record copies.  Fit: 1.368 ms per sweep at 16 sweeps per replay
+        vs 1.373-1.375 at one (the flat one-copy record in both), 1.374-1.383 at 32
+        (profiles/r05/r05_block_fit.log): the host keeps the queue full either way."""
+        B = self.block
+        if not hasattr(self, "_ublk"):
+            self._ublk = torch.zeros((B, self.C, self.nu), dtype=F64, device=self.dev)
+            self._rblk = torch.zeros((B,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        u0 = self.u
+        try:
+            with torch.cuda.graph(g):
+                for j in range(B):
+                    self.u = self._ublk[j]
+                    self._sweep()
+                    if record:
+                        self._rblk[j].copy_(self._flat)
+        finally:
+            self.u = u0
+        self._bgraph[record] = g
+
+    # -- chains --------------------------------------------------------------------------
+    def _run(self, nsamp: int, rngs: list, record: bool = True, block: int = 64):
+        """``nsamp`` sweeps of every chain from the current states (init_state() first if there
+        are none); chain c consumes ``rngs[c].random((rows, nu))`` in blocks of ``block`` rows.
+        Returns, when ``record``, the samples dict (numpy) with a leading chain axis: betaU
+        (C, N, (d+1) P), lamUz, lamWs (C, N, P), lamWOs, logPost (C, N, 1)."""
+        if len(rngs) != self.C:
+            raise ValueError(f"{len(rngs)} generators for {self.C} chains")
+        if self.st is None:
+            self.init_state()
+        if record:
+            rec = torch.empty((nsamp,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
+        B = self.block if self.use_graph and self.block > 1 else 0
+        for a in range(0, nsamp, block):
+            b = min(nsamp, a + block)
+            U = self._t(np.stack([r.random((b - a, self.nu)) for r in rngs], axis=1))
+            i = a
+            while B and b - i >= B:                     # whole graph blocks
+                if record not in self._bgraph:
+                    self._capture_block(record)
+                self._ublk.copy_(U[i - a:i - a + B])
+                self._bgraph[record].replay()
+                if record:
+                    rec[i:i + B].copy_(self._rblk)
+                i += B
+            for i in range(i, b):                       # the rest one sweep at a time
+                self.u.copy_(U[i - a])
+                self.sweep()
+                if record:
+                    rec[i].copy_(self._flat)
+        # one host check per run: a factorisation that gave up (info = -1) would otherwise be a
+        # silently rejected proposal (ll = NaN); a non-PD proposal (ll = -inf) is a rejection
+        for ws in self._ws.values():
+            ws.check_status()
+        if not record:
+            return None
+        rec = rec.cpu().numpy().transpose(1, 0, 2)
+        return {k: rec[:, :, a:b].copy() for k, (a, b) in self._cols.items()}
+
+
+class GPUSampler(_ChainSweeps):
+    """Component-wise Metropolis over the P PC-GPs of one emulator, all state on the device: the
+    one-chain case of _ChainSweeps, plus the tensor-op form of the sweep.
 
     One sweep is ~11 batched gp_loglik calls plus elementwise proposal / accept work: a few
     hundred small launches.  By default (``use_graph`` None; GPFIT_MCMC_GRAPH=0 opts out) the
@@ -207,142 +496,52 @@ class GPUSampler:
 
     ``spec`` (default: default_spec(n, P, d + 3); GPFIT_MCMC_SPEC overrides): likelihood-
     changing updates per batched gp_loglik, evaluated speculatively for every outcome of the
-    group's earlier updates (see _sweep).  At n = 512 a factorisation is latency-bound (its
+    group's earlier updates (see _sweep_torch).  At n = 512 a factorisation is latency-bound (its
     64-column chain), so evaluating 3P problems costs about what P did: spec 2 took a sweep from
     11 gp_loglik calls to 6, 3.79 -> 2.86 ms per sweep (profiles/r03/ab_mcmc_spec.log).  With
     the in-chain likelihood (round 6) 7P = 56 problems cost 0.26 ms per call against 0.21 for
     24, so spec 3 (4 calls) wins at P = 8: 1.278 -> 1.054 ms per sweep, the fit 1.67 -> 1.41-1.44
     s (profiles/r06/r06al_ab_spec.log).
+
+    ``fused`` (default on a HIP device; GPFIT_MCMC_FUSED=0 opts out): the sweep of the kernels in
+    csrc/mcmc.hip; otherwise, and on any other device, the tensor-op sweep.
     """
 
     def __init__(self, X: torch.Tensor, w_hat: torch.Tensor, LamSim: torch.Tensor,
                  params: ModelParams, use_graph: bool | None = None, spec: int | None = None,
                  fused: bool | None = None):
-        self.X = X.contiguous()
         self.w = w_hat.contiguous()                 # (P, n)
-        self.P, self.n = self.w.shape
-        self.d = self.X.shape[1]
-        self.dev = self.X.device
-        self.lam = LamSim.to(self.dev, F64).reshape(self.P).contiguous()
-        self.params = params
-        self.ws = kernels.LoglikWorkspace(self.n, self.P, self.dev)
-        self._beta = torch.empty((self.P, self.d), dtype=F64, device=self.dev)
-        self._s = torch.empty(self.P, dtype=F64, device=self.dev)
-        self._delta = torch.empty(self.P, dtype=F64, device=self.dev)
-        self._ll = torch.empty(self.P, dtype=F64, device=self.dev)
-        self.nu = uniforms_per_sweep(self.d, self.P)
-        self.u = torch.zeros(self.nu, dtype=F64, device=self.dev)        # static uniforms
-        self.steps = {k: self._t(getattr(params, k).mcmcStepParam) for k in ModelParams.names}
-        # the recorded state, one flat row: betaU (d+1, P) | lamUz | lamWs | lamWOs | log post
-        # (ChainState's tensors are views of it, so a sample is recorded with one copy)
-        P_, d_ = self.P, self.d
-        self._cols = {"betaU": (0, (d_ + 1) * P_)}
-        o_ = (d_ + 1) * P_
-        for k_, w_ in (("lamUz", P_), ("lamWs", P_), ("lamWOs", 1), ("logPost", 1)):
-            self._cols[k_] = (o_, o_ + w_)
-            o_ += w_
-        self._flat = torch.zeros(o_, dtype=F64, device=self.dev)
-        self.lp = self._flat[self._cols["logPost"][0]:]                 # log posterior
-        if use_graph is None:
-            use_graph = os.environ.get("GPFIT_MCMC_GRAPH", "1") == "1"
-        self.use_graph = use_graph and self.dev.type == "cuda"
-        self.graph = None
-        # sweeps per replayed graph in run() (GPFIT_MCMC_BLOCK; 1: one sweep per replay)
-        self.block = max(1, int(os.environ.get("GPFIT_MCMC_BLOCK", "16")))
-        # decide + next prep in one launch (gp_mcmc_group_step); GPFIT_MCMC_MERGE=0: two
-        self._merge = os.environ.get("GPFIT_MCMC_MERGE", "1") == "1"
-        self._bgraph = {}
-        self.st = None
+        P, n = self.w.shape
         if spec is None:
-            spec = int(os.environ.get("GPFIT_MCMC_SPEC", "0")) or default_spec(self.n, self.P,
-                                                                               self.d + 3)
+            spec = int(os.environ.get("GPFIT_MCMC_SPEC", "0")) or default_spec(n, P,
+                                                                               X.shape[1] + 3)
         if spec < 1:
             raise ValueError("spec (updates per speculative group) must be >= 1")
-        # the likelihood-changing updates of a sweep, in mcmcList order (betaU row 0, the
-        # dummy x, moves under its prior alone)
-        ups = [("betaU", k) for k in range(1, self.d + 1)] + [(nm, None) for nm in
-                                                               ("lamUz", "lamWs", "lamWOs")]
-        self.groups = [ups[i:i + spec] for i in range(0, len(ups), spec)]
-        self.spec = spec
         if fused is None:
             fused = os.environ.get("GPFIT_MCMC_FUSED", "1") == "1"
-        self.fused = fused and self.dev.type == "cuda"
-        if self.fused and spec > _capi.MCMC_MAX_GROUP:
+        fused = fused and X.device.type == "cuda"
+        if fused and spec > _capi.MCMC_MAX_GROUP:
             raise ValueError(f"spec > {_capi.MCMC_MAX_GROUP} needs fused=False")
-        self._S = None
-        self._scratch = torch.zeros(3 * _capi.MCMC_MAX_GROUP * self.P, dtype=F64, device=self.dev)
-        self._gbuf = {}
-        for g in self.groups:
-            sets = 2 ** len(g) - 1
-            if sets not in self._gbuf:
-                B = sets * self.P
-                self._gbuf[sets] = dict(
-                    ws=self.ws if B == self.P else kernels.LoglikWorkspace(self.n, B, self.dev),
-                    beta=torch.empty((B, self.d), dtype=F64, device=self.dev),
-                    s=torch.empty(B, dtype=F64, device=self.dev),
-                    delta=torch.empty(B, dtype=F64, device=self.dev),
-                    ll=torch.empty(B, dtype=F64, device=self.dev),
-                    w=self.w.repeat(sets, 1).contiguous())
-
-    def _t(self, a) -> torch.Tensor:
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.dev)
+        super().__init__(X, self.w[None], LamSim, [params], use_graph, spec, fused, None)
+        self.params = params
+        self.lp = self._view("logPost")[0]          # log posterior
 
     # -- state ---------------------------------------------------------------------------
     def init_state(self) -> ChainState:
-        """Chain state from params' current values (allocated once; later calls copy)."""
-        pr = self.params
-        vals = (self._t(pr.betaU.val), self._t(pr.lamUz.val).reshape(self.P),
-                self._t(pr.lamWs.val).reshape(self.P), self._t(pr.lamWOs.val).reshape(1))
+        """Chain state from params' current values (its views are made once; later calls copy)."""
         if self.st is None:
-            z = torch.zeros(self.P, dtype=F64, device=self.dev)
-            views = []
-            for k, v in zip(("betaU", "lamUz", "lamWs", "lamWOs"), vals):
-                a, b = self._cols[k]
-                t = self._flat[a:b].view(v.shape)
-                t.copy_(v)
-                views.append(t)
-            self.st = ChainState(*views, z.clone())
-            # one (d + 4, P) block indexed by update code (gp_mcmc_state.acc), viewed per update
-            d = self.d
-            self._acc = torch.zeros((d + 4, self.P), dtype=F64, device=self.dev)
-            self.st.acc = {("betaU", k): self._acc[k] for k in range(d + 1)}
-            self.st.acc.update({"lamUz": self._acc[d + 1], "lamWs": self._acc[d + 2],
-                                "lamWOs": self._acc[d + 3, :1]})
-        else:
-            for t, v in zip((self.st.betaU, self.st.lamUz, self.st.lamWs, self.st.lamWOs),
-                            vals):
-                t.copy_(v)
-        self.st.ll.copy_(self.loglik(self.st.betaU, self.st.lamUz, self.st.lamWs,
-                                     self.st.lamWOs))
-        self.reset_counts()
+            d, P, acc = self.d, self.P, self._acc[0]
+            views = [self._view(k)[0].view(shape) for k, shape in
+                     (("betaU", (d + 1, P)), ("lamUz", P), ("lamWs", P), ("lamWOs", 1))]
+            self.st = ChainState(*views, self._ll[0])
+            self.st.acc = {("betaU", k): acc[k] for k in range(d + 1)}
+            self.st.acc.update({"lamUz": acc[d + 1], "lamWs": acc[d + 2],
+                                "lamWOs": acc[d + 3, :1]})
+        super().init_state()
         return self.st
 
-    def reset_counts(self) -> None:
-        for c in self.st.acc.values():
-            c.zero_()
-
     def counts(self) -> dict:
-        return {k: v.cpu().numpy() for k, v in self.st.acc.items()}
-
-    def set_steps(self, scale: float = 1.0) -> None:
-        for k in ModelParams.names:
-            self.steps[k].copy_(self._t(getattr(self.params, k).mcmcStepParam * scale))
-
-    def write_back(self) -> None:
-        pr, st = self.params, self.st
-        pr.betaU.val = st.betaU.cpu().numpy().reshape(pr.betaU.val_shape)
-        pr.lamUz.val = st.lamUz.cpu().numpy().reshape(pr.lamUz.val_shape)
-        pr.lamWs.val = st.lamWs.cpu().numpy().reshape(pr.lamWs.val_shape)
-        pr.lamWOs.val = st.lamWOs.cpu().numpy().reshape(pr.lamWOs.val_shape)
-
-    # -- likelihood / posterior ----------------------------------------------------------
-    def loglik(self, betaU, lamUz, lamWs, lamWOs) -> torch.Tensor:
-        """Per-GP log-likelihood (P,) for the given parameters (one gp_loglik call)."""
-        self._beta.copy_(betaU[1:].transpose(0, 1))
-        torch.reciprocal(lamUz, out=self._s)
-        torch.add(torch.reciprocal(lamWs), torch.reciprocal(lamWOs * self.lam), out=self._delta)
-        return kernels.loglik(self.X, self._beta, self._s, self._delta, self.w, self.ws,
-                              out=self._ll)
+        return self._counts()[0]
 
     def log_post(self) -> torch.Tensor:
         pr, st = self.params, self.st
@@ -358,7 +557,7 @@ class GPUSampler:
         sl = slice(slot * self.P, (slot + 1) * self.P)
         buf["beta"][sl].copy_(st["betaU"][1:].transpose(0, 1))
         torch.reciprocal(st["lamUz"], out=buf["s"][sl])
-        torch.add(torch.reciprocal(st["lamWs"]), torch.reciprocal(st["lamWOs"] * self.lam),
+        torch.add(torch.reciprocal(st["lamWs"]), torch.reciprocal(st["lamWOs"] * self.lam[0]),
                   out=buf["delta"][sl])
 
     @staticmethod
@@ -374,16 +573,22 @@ class GPUSampler:
             out[name] = cand
         return out
 
+    def _update(self, code: int):
+        """(parameter name, betaU row or None) of an update code."""
+        d = self.d
+        return ("betaU", code) if code <= d else (("lamUz", "lamWs", "lamWOs")[code - d - 1], None)
+
     def _propose(self, u, take):
-        pr, st, steps, P = self.params, self.st, self.steps, self.P
+        pr, st, P = self.params, self.st, self.P
         name, k = u
         p = getattr(pr, name)
+        step = self.steps[name][0]
         if name == "betaU":
-            cur, step, m = st.betaU[k], steps["betaU"][k], P
+            cur, step, m = st.betaU[k], step[k], P
         elif name == "lamWOs":
-            cur, step, m = st.lamWOs, steps["lamWOs"].reshape(1), 1
+            cur, step, m = st.lamWOs, step.reshape(1), 1
         else:
-            cur, step, m = getattr(st, name), steps[name].reshape(P), P
+            cur, step, m = getattr(st, name), step.reshape(P), P
         up, ua = take(m), take(m)
         cand, ok = propose(p, cur, step, up)
         return cand, ok, log_prior(p, cand) - log_prior(p, cur), ua, cur
@@ -402,71 +607,11 @@ class GPUSampler:
         st.acc[("betaU", k) if name == "betaU" else name].add_(acc.to(F64))
         return acc
 
-    def _code(self, u) -> int:
-        name, k = u
-        return k if name == "betaU" else self.d + {"lamUz": 1, "lamWs": 2, "lamWOs": 3}[name]
-
-    def _state_struct(self) -> "_capi.McmcState":
-        """gp_mcmc_state over the static buffers and the current priors."""
-        st, pr = self.st, self.params
-        S = _capi.McmcState()
-        for nm, t in (("betaU", st.betaU), ("lamUz", st.lamUz), ("lamWs", st.lamWs),
-                      ("lamWOs", st.lamWOs), ("ll", st.ll), ("lam", self.lam), ("u", self.u),
-                      ("step_betaU", self.steps["betaU"]), ("step_lamUz", self.steps["lamUz"]),
-                      ("step_lamWs", self.steps["lamWs"]), ("step_lamWOs", self.steps["lamWOs"]),
-                      ("acc", self._acc), ("lp", self.lp), ("scratch", self._scratch)):
-            if not t.is_contiguous() or t.dtype != F64:
-                raise TypeError(f"mcmc state buffer {nm} must be contiguous float64")
-            setattr(S, nm, t.data_ptr())
-        S.P, S.d = self.P, self.d
-        for i, nm in enumerate(ModelParams.names):
-            p = getattr(pr, nm)
-            S.dist[i] = _capi.MCMC_DIST[p.dist]
-            S.steptype[i] = _capi.MCMC_STEP[p.mcmcStepType]
-            S.pa[i], S.pb[i] = p.params
-            S.lo[i], S.hi[i] = p.bounds
-        return S
-
     def _sweep(self) -> None:
         if self.fused:
-            self._sweep_fused()
+            super()._sweep()
         else:
             self._sweep_torch()
-
-    def _sweep_fused(self) -> None:
-        """The sweep of _sweep_torch with each speculative group's proposals and decisions in
-        single-workgroup kernels around its gp_loglik (csrc/mcmc.hip): the first group's
-        gp_mcmc_group_prep, then after each gp_loglik one gp_mcmc_group_step (this group's
-        decisions + the next group's proposals; gp_mcmc_group_decide after the last), so
-        2 + gp_loglik's launches per group instead of ~100."""
-        self._S = self._state_struct()          # kept alive: the library reads it per call
-        S = ctypes.addressof(self._S)
-        stream = kernels._stream(self.dev)
-        last = len(self.groups) - 1
-        kinds = [(ctypes.c_int * len(g))(*[self._code(u) for u in g]) for g in self.groups]
-        self._kinds = kinds                     # (kept alive with _S)
-        bufs = [self._gbuf[2 ** len(g) - 1] for g in self.groups]
-        b0 = bufs[0]
-        _capi.call("gp_mcmc_group_prep", S, ctypes.addressof(kinds[0]), len(self.groups[0]), 1,
-                   b0["beta"].data_ptr(), b0["s"].data_ptr(), b0["delta"].data_ptr(), stream)
-        for gi, grp in enumerate(self.groups):
-            buf = bufs[gi]
-            kernels.loglik(self.X, buf["beta"], buf["s"], buf["delta"], buf["w"], buf["ws"],
-                           out=buf["ll"])
-            if gi == last or not self._merge:
-                _capi.call("gp_mcmc_group_decide", S, ctypes.addressof(kinds[gi]), len(grp),
-                           int(gi == last), buf["ll"].data_ptr(), stream)
-                if gi < last:
-                    nb = bufs[gi + 1]
-                    _capi.call("gp_mcmc_group_prep", S, ctypes.addressof(kinds[gi + 1]),
-                               len(self.groups[gi + 1]), 0, nb["beta"].data_ptr(),
-                               nb["s"].data_ptr(), nb["delta"].data_ptr(), stream)
-            else:
-                nb = bufs[gi + 1]
-                _capi.call("gp_mcmc_group_step", S, ctypes.addressof(kinds[gi]), len(grp), 0,
-                           buf["ll"].data_ptr(), S, ctypes.addressof(kinds[gi + 1]),
-                           len(self.groups[gi + 1]), 0, nb["beta"].data_ptr(),
-                           nb["s"].data_ptr(), nb["delta"].data_ptr(), stream)
 
     def _sweep_torch(self) -> None:
         """One component-wise Metropolis sweep on the static buffers (graph-capturable: no
@@ -482,7 +627,7 @@ class GPUSampler:
         sweep, so the chain is the same Markov chain, draw for draw; what changes is that the
         factorisations, whose latency (a 64-column chain step per tile) bounds a sweep at
         n = 512, are issued g at a time (spec = 1: one call per update)."""
-        pr, st, P, u = self.params, self.st, self.P, self.u
+        st, P, u = self.st, self.P, self.u[0]
         o = 0
 
         def take(k):
@@ -496,9 +641,11 @@ class GPUSampler:
         acc = ok & (torch.log(ua) < dlp)
         cur.copy_(torch.where(acc, cand, cur))
         st.acc[("betaU", 0)].add_(acc.to(F64))
-        for grp in self.groups:
+        for codes in self.groups:
+            grp = [self._update(c) for c in codes]
             props = [self._propose(g, take) for g in grp]
-            buf = self._gbuf[2 ** len(grp) - 1]
+            sets = 2 ** len(grp) - 1
+            buf = self._gbuf[sets]
             s0 = {"betaU": st.betaU, "lamUz": st.lamUz, "lamWs": st.lamWs, "lamWOs": st.lamWOs}
             slot, base = 0, []
             for i, g in enumerate(grp):
@@ -510,8 +657,8 @@ class GPUSampler:
                             sx = self._with(sx, grp[j], props[j][0])
                     self._fill(buf, slot, self._with(sx, g, props[i][0]))
                     slot += 1
-            ll_all = kernels.loglik(self.X, buf["beta"], buf["s"], buf["delta"], buf["w"],
-                                    buf["ws"], out=buf["ll"]).view(-1, P)
+            self._loglik(sets)
+            ll_all = buf["ll"].view(-1, P)
             pat = None
             for i, g in enumerate(grp):
                 ll_i = ll_all[base[i]:base[i] + 2 ** i]
@@ -520,81 +667,13 @@ class GPUSampler:
                 pat = acc if pat is None else pat + acc
         self.lp.copy_(self.log_post().reshape(1))
 
-    def _capture(self) -> None:
-        """Record one sweep as a graph (capture does not execute it: the chain is untouched)."""
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._sweep()
-        self.graph = g
-
-    def sweep(self) -> None:
-        if self.use_graph:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-        else:
-            self._sweep()
-
-    def _capture_block(self, record: bool) -> None:
-        """Record ``block`` sweeps as one graph: sweep j reads the uniforms of row j of a static
-        block and (``record``) copies the flat state into row j of a static record block.  One
-        replay per block instead of one per sweep, and one copy per recorded sample instead of
-        one uniform upload + five record copies.  Fit: 1.368 ms per sweep at 16 sweeps per replay
-        vs 1.373-1.375 at one (the flat one-copy record in both), 1.374-1.383 at 32
-        (profiles/r05/r05_block_fit.log): the host keeps the queue full either way."""
-        B = self.block
-        if not hasattr(self, "_ublk"):
-            self._ublk = torch.zeros((B, self.nu), dtype=F64, device=self.dev)
-            self._rblk = torch.zeros((B, self._flat.numel()), dtype=F64, device=self.dev)
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        u0 = self.u
-        try:
-            with torch.cuda.graph(g):
-                for j in range(B):
-                    self.u = self._ublk[j]
-                    self._sweep()
-                    if record:
-                        self._rblk[j].copy_(self._flat)
-        finally:
-            self.u = u0
-        self._bgraph[record] = g
-
     # -- chains --------------------------------------------------------------------------
     def run(self, nsamp: int, rng: np.random.Generator, record: bool = True, block: int = 64):
         """``nsamp`` sweeps from the current state (init_state() first if there is none);
-        returns the samples dict (numpy) when ``record``."""
-        if self.st is None:
-            self.init_state()
-        if record:
-            rec = torch.empty((nsamp, self._flat.numel()), dtype=F64, device=self.dev)
-        B = self.block if self.use_graph and self.block > 1 else 0
-        for a in range(0, nsamp, block):
-            b = min(nsamp, a + block)
-            U = self._t(rng.random((b - a, self.nu)))
-            i = a
-            while B and b - i >= B:                     # whole graph blocks
-                if record not in self._bgraph:
-                    self._capture_block(record)
-                self._ublk.copy_(U[i - a:i - a + B])
-                self._bgraph[record].replay()
-                if record:
-                    rec[i:i + B].copy_(self._rblk)
-                i += B
-            for i in range(i, b):                       # the rest one sweep at a time
-                self.u.copy_(U[i - a])
-                self.sweep()
-                if record:
-                    rec[i].copy_(self._flat)
-        # one host check per run: a factorisation that gave up (info = -1) would otherwise be a
-        # silently rejected proposal (ll = NaN); a non-PD proposal (ll = -inf) is a rejection
-        for ws in {id(w): w for w in [self.ws] + [b["ws"] for b in self._gbuf.values()]}.values():
-            ws.check_status()
-        if not record:
-            return None
-        rec = rec.cpu().numpy()
-        return {k: rec[:, a:b].copy() for k, (a, b) in self._cols.items()}
+        returns the samples dict (numpy), betaU (N, (d+1) P) ... logPost (N, 1), when
+        ``record``."""
+        rec = self._run(nsamp, [rng], record, block)
+        return {k: v[0] for k, v in rec.items()} if record else None
 
 
 # --------------------------------------------------------------------------- step tuning
@@ -639,8 +718,8 @@ def _ladder(n_levels: int) -> np.ndarray:
 
 
 def _fit_chain_steps(pr: ModelParams, base: dict, ex: np.ndarray, counts: list, n_burn: int):
-    """The per-element logistic fits of one chain (tune_step_sizes and
-    tune_step_sizes_ensemble): ``counts`` holds one sampler.counts() dict per ladder level,
+    """The per-element logistic fits of one chain (_tune): ``counts`` holds the chain's counts
+    dict (GPUSampler.counts()) per ladder level,
     ``base`` the steps the ladder scaled.  Returns (new steps per parameter, the tune record)."""
     logs = {k: np.log(base[k][None] * (2.0 ** ex).reshape((-1,) + (1,) * base[k].ndim))
             for k in base}
@@ -677,31 +756,40 @@ def _fit_chain_steps(pr: ModelParams, base: dict, ex: np.ndarray, counts: list, 
     return new, info
 
 
-def tune_step_sizes(sampler: GPUSampler, n_burn: int, n_levels: int,
-                    rng: np.random.Generator) -> None:
-    """GPMSA-style step-size tuning (see module doc); updates params' mcmcStepParam in place
-    and leaves the sampler's chain at the state reached."""
-    pr = sampler.params
+def _tune(sampler: _ChainSweeps, n_burn: int, n_levels: int, rngs: list) -> list:
+    """GPMSA-style step-size tuning (see module doc) of every chain of ``sampler``, stepped
+    together: updates each chain's params' mcmcStepParam in place, leaves the chains at the
+    states reached and returns the per-chain tune records."""
     if sampler.st is None:
         sampler.init_state()
     ex = _ladder(n_levels)
-    base = {k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
+    bases = [{k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
+             for pr in sampler._params]
     # burn-in at the default steps first: acceptance counted while the chain is still
     # travelling from the start values would make the smallest-step level look worst
     sampler.set_steps(1.0)
-    sampler.run(n_burn, rng, record=False)
+    sampler._run(n_burn, rngs, record=False)
     counts = []
     for e in ex:
         sampler.set_steps(2.0 ** e)
         sampler.reset_counts()
-        sampler.run(n_burn, rng, record=False)
-        counts.append(sampler.counts())
-    new, info = _fit_chain_steps(pr, base, ex, counts, n_burn)
-    for k in base:
-        getattr(pr, k).mcmcStepParam = new[k]
+        sampler._run(n_burn, rngs, record=False)
+        counts.append(sampler._counts())
+    infos = []
+    for c, pr in enumerate(sampler._params):
+        new, info = _fit_chain_steps(pr, bases[c], ex, [lev[c] for lev in counts], n_burn)
+        for k in new:
+            getattr(pr, k).mcmcStepParam = new[k]
+        infos.append(info)
     sampler.set_steps(1.0)
     sampler.reset_counts()
-    sampler.last_tune = info
+    return infos
+
+
+def tune_step_sizes(sampler: GPUSampler, n_burn: int, n_levels: int,
+                    rng: np.random.Generator) -> None:
+    """Tune the lone sampler's steps (_tune); ``sampler.last_tune`` is the tune record."""
+    sampler.last_tune = _tune(sampler, n_burn, n_levels, [rng])[0]
 
 
 # ------------------------------------------------------------------------ ensemble sampler
@@ -747,7 +835,7 @@ def loglik_max_batch(n: int, dev: torch.device) -> int | None:
     return best
 
 
-class EnsembleSampler:
+class EnsembleSampler(_ChainSweeps):
     """C chains stepped together: one gp_mcmc_ens_* launch of C workgroups around each batched
     gp_loglik of all chains' state sets, instead of C GPUSamplers one after another.
 
@@ -756,326 +844,73 @@ class EnsembleSampler:
     counters and uniforms (``params[c]``: a ModelParams holding chain c's values and steps).  C
     repeat chains of one model and C scalar models on one design are the same thing with equal
     or different ``w_hat``.  Chain c is the Markov chain a lone GPUSampler produces from the same
-    generator: the kernels run GPUSampler's code per chain (csrc/mcmc.hip), and a likelihood
-    does not depend on the batch it is evaluated in.
+    generator: both run _ChainSweeps' sweep, and a chain does not depend on the others.
 
-    Fused sweep only, on a HIP device.  The batch is chain-major, and gp_loglik is issued in
-    slices of whole chains of at most ``max_batch`` problems: by default the largest batch the
+    Fused sweep only, on a HIP device.  ``max_batch`` is by default the largest batch the
     persistent factorisation takes (loglik_max_batch; beyond it gp_loglik falls back to a much
     slower path).  The default group size starts from default_spec(n, C P, d + 3) and is lowered
-    while one chain's (2^spec - 1) P problems exceed ``max_batch``.  Slices of equal size share
-    one workspace (the workspace's layout depends on its batch, so sizes cannot share).
+    while one chain's (2^spec - 1) P problems exceed ``max_batch``.
     """
 
     def __init__(self, X: torch.Tensor, w_hat: torch.Tensor, LamSim: torch.Tensor, params: list,
                  use_graph: bool | None = None, spec: int | None = None,
                  max_batch: int | None = None):
-        self.X = X.contiguous()
-        self.dev = self.X.device
-        if self.dev.type != "cuda":
+        if X.device.type != "cuda":
             raise ValueError("EnsembleSampler runs the fused sweep: it needs a HIP device")
-        self.w = w_hat.to(self.dev, F64).contiguous()                   # (C, P, n)
+        self.w = w_hat.to(X.device, F64).contiguous()                   # (C, P, n)
         if self.w.dim() != 3:
             raise ValueError("w_hat must be (C, P, n)")
-        self.C, self.P, self.n = self.w.shape
-        self.d = self.X.shape[1]
-        params = list(params)
-        if len(params) != self.C:
-            raise ValueError(f"{len(params)} ModelParams for {self.C} chains")
-        if not 1 <= self.C <= _capi.MCMC_MAX_CHAINS:
+        C, P, n = self.w.shape
+        d = X.shape[1]
+        self.params = params = list(params)
+        if len(params) != C:
+            raise ValueError(f"{len(params)} ModelParams for {C} chains")
+        if not 1 <= C <= _capi.MCMC_MAX_CHAINS:
             raise ValueError(f"1 .. {_capi.MCMC_MAX_CHAINS} chains (GPFIT_MCMC_MAX_CHAINS)")
         check_shared_priors(params)
-        if params[0].betaU.val_shape != (self.d + 1, self.P):
+        if params[0].betaU.val_shape != (d + 1, P):
             raise ValueError(f"params are for (d, P) = ({params[0].betaU.val_shape[0] - 1}, "
-                             f"{params[0].betaU.val_shape[1]}), the data for ({self.d}, {self.P})")
-        if self.X.shape[0] != self.n:
+                             f"{params[0].betaU.val_shape[1]}), the data for ({d}, {P})")
+        if X.shape[0] != n:
             raise ValueError("X and w_hat disagree on n")
-        self.params = params
-        C, P, d = self.C, self.P, self.d
-        self.lam = LamSim.to(self.dev, F64).reshape(C, P).contiguous()
-        self.nu = uniforms_per_sweep(d, P)
-        self.u = torch.zeros((C, self.nu), dtype=F64, device=self.dev)
-        self.steps = {k: torch.zeros((C,) + getattr(params[0], k).val_shape, dtype=F64,
-                                     device=self.dev) for k in ModelParams.names}
-        self.set_steps(1.0)
-        # the recorded state, one flat row per chain, laid out as GPUSampler's
-        self._cols = {"betaU": (0, (d + 1) * P)}
-        o = (d + 1) * P
-        for k, w_ in (("lamUz", P), ("lamWs", P), ("lamWOs", 1), ("logPost", 1)):
-            self._cols[k] = (o, o + w_)
-            o += w_
-        self._flat = torch.zeros((C, o), dtype=F64, device=self.dev)
-        self._ll = torch.zeros((C, P), dtype=F64, device=self.dev)
-        self._acc = torch.zeros((C, d + 4, P), dtype=F64, device=self.dev)
-        self._scratch = torch.zeros((C, 3 * _capi.MCMC_MAX_GROUP * P), dtype=F64,
-                                    device=self.dev)
-        self.st = None
-        if use_graph is None:
-            use_graph = os.environ.get("GPFIT_MCMC_GRAPH", "1") == "1"
-        self.use_graph = bool(use_graph)
-        self.graph = None
-        self.block = max(1, int(os.environ.get("GPFIT_MCMC_BLOCK", "16")))
-        self._merge = os.environ.get("GPFIT_MCMC_MERGE", "1") == "1"
-        self._bgraph = {}
         # slices of whole chains within the persistent factorisation's range
-        limit = loglik_max_batch(self.n, self.dev) if max_batch is None else int(max_batch)
-        self.max_batch = C * (2 ** _capi.MCMC_MAX_GROUP - 1) * P if limit is None else limit
-        if P > self.max_batch:
+        limit = loglik_max_batch(n, X.device) if max_batch is None else int(max_batch)
+        max_batch = C * (2 ** _capi.MCMC_MAX_GROUP - 1) * P if limit is None else limit
+        if P > max_batch:
             raise ValueError(f"one chain's {P} GPs do not fit a gp_loglik batch of at most "
-                             f"{self.max_batch} problems (max_batch; by default the persistent "
+                             f"{max_batch} problems (max_batch; by default the persistent "
                              "factorisation's range on this stream)")
         given = spec if spec is not None else int(os.environ.get("GPFIT_MCMC_SPEC", "0"))
         if given:
             if not 1 <= given <= _capi.MCMC_MAX_GROUP:
                 raise ValueError(f"spec must be 1 .. {_capi.MCMC_MAX_GROUP}")
-            if (2 ** given - 1) * P > self.max_batch:
+            if (2 ** given - 1) * P > max_batch:
                 raise ValueError(f"spec {given}: one chain's {(2 ** given - 1) * P} problems "
-                                 f"exceed the gp_loglik batch limit {self.max_batch}")
+                                 f"exceed the gp_loglik batch limit {max_batch}")
             spec = given
         else:
-            spec = default_spec(self.n, C * P, d + 3)
-            while (2 ** spec - 1) * P > self.max_batch:
+            spec = default_spec(n, C * P, d + 3)
+            while (2 ** spec - 1) * P > max_batch:
                 spec -= 1
-        self.spec = spec
-        codes = list(range(1, d + 4))
-        self.groups = [codes[i:i + spec] for i in range(0, len(codes), spec)]
-        self._ws = {}
-        self._gbuf = {}
-        for sets in {1} | {2 ** len(g) - 1 for g in self.groups}:   # 1: init_state's call
-            R = sets * P
-            self._gbuf[sets] = dict(
-                chunk=max(1, self.max_batch // R),
-                beta=torch.empty((C * R, d), dtype=F64, device=self.dev),
-                s=torch.empty(C * R, dtype=F64, device=self.dev),
-                delta=torch.empty(C * R, dtype=F64, device=self.dev),
-                ll=torch.empty(C * R, dtype=F64, device=self.dev),
-                w=self.w[:, None].expand(C, sets, P, self.n).reshape(C * R, self.n).contiguous())
-            for c0 in range(0, C, self._gbuf[sets]["chunk"]):
-                B = (min(C, c0 + self._gbuf[sets]["chunk"]) - c0) * R
-                if B not in self._ws:
-                    self._ws[B] = kernels.LoglikWorkspace(self.n, B, self.dev)
-        T = self._T = _capi.McmcStrides()
-        T.betaU = T.lamUz = T.lamWs = T.lamWOs = T.lp = self._flat.shape[1]
-        T.ll, T.lam, T.u, T.acc, T.scratch = P, P, self.nu, (d + 4) * P, self._scratch.shape[1]
-        T.step_betaU, T.step_lamUz, T.step_lamWs, T.step_lamWOs = (d + 1) * P, P, P, 1
-        self._kinds = [(ctypes.c_int * len(g))(*g) for g in self.groups]
-
-    def _t(self, a) -> torch.Tensor:
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self.dev)
-
-    def _view(self, name: str) -> torch.Tensor:
-        a, b = self._cols[name]
-        return self._flat[:, a:b]
-
-    # -- state (per chain) ---------------------------------------------------------------
-    def init_state(self) -> None:
-        """Every chain's state from its params' current values, ll from one sliced gp_loglik."""
-        C, P, d = self.C, self.P, self.d
-        for k in ModelParams.names:
-            self._view(k).copy_(self._t(np.stack([getattr(pr, k).val.reshape(-1)
-                                                  for pr in self.params])))
-        buf = self._gbuf[1]
-        betaU = self._view("betaU").reshape(C, d + 1, P)
-        buf["beta"].view(C, P, d).copy_(betaU[:, 1:].transpose(1, 2))
-        torch.reciprocal(self._view("lamUz"), out=buf["s"].view(C, P))
-        torch.add(torch.reciprocal(self._view("lamWs")),
-                  torch.reciprocal(self._view("lamWOs") * self.lam), out=buf["delta"].view(C, P))
-        self._loglik(1)
-        self._ll.copy_(buf["ll"].view(C, P))
-        self.st = self._flat                    # the states: one flat row per chain
-        self.reset_counts()
-
-    def reset_counts(self) -> None:
-        self._acc.zero_()
+        super().__init__(X, self.w, LamSim, params, use_graph, spec, True, max_batch)
 
     def counts(self) -> list:
         """Per chain, GPUSampler.counts()'s dict."""
-        a, d = self._acc.cpu().numpy(), self.d
-        out = []
-        for c in range(self.C):
-            cnt = {("betaU", k): a[c, k].copy() for k in range(d + 1)}
-            cnt.update({"lamUz": a[c, d + 1].copy(), "lamWs": a[c, d + 2].copy(),
-                        "lamWOs": a[c, d + 3, :1].copy()})
-            out.append(cnt)
-        return out
+        return self._counts()
 
-    def set_steps(self, scale: float = 1.0) -> None:
-        for k in ModelParams.names:
-            self.steps[k].copy_(self._t(np.stack([getattr(pr, k).mcmcStepParam * scale
-                                                  for pr in self.params])))
-
-    def write_back(self) -> None:
-        flat = self._flat.cpu().numpy()
-        for c, pr in enumerate(self.params):
-            for k in ModelParams.names:
-                a, b = self._cols[k]
-                p = getattr(pr, k)
-                p.val = flat[c, a:b].reshape(p.val_shape).copy()
-
-    # -- one sweep -----------------------------------------------------------------------
-    def _loglik(self, sets: int) -> None:
-        """gp_loglik over the chain-major batch of ``sets`` state sets per chain, in slices of
-        whole chains."""
-        buf, R = self._gbuf[sets], sets * self.P
-        for c0 in range(0, self.C, buf["chunk"]):
-            r0, r1 = c0 * R, min(self.C, c0 + buf["chunk"]) * R
-            kernels.loglik(self.X, buf["beta"][r0:r1], buf["s"][r0:r1], buf["delta"][r0:r1],
-                           buf["w"][r0:r1], self._ws[r1 - r0], out=buf["ll"][r0:r1])
-
-    def _state_struct(self) -> "_capi.McmcState":
-        """gp_mcmc_state of chain 0 over the static buffers (self._T: the strides)."""
-        pr = self.params[0]
-        S = _capi.McmcState()
-        for nm, t in (("betaU", self._view("betaU")), ("lamUz", self._view("lamUz")),
-                      ("lamWs", self._view("lamWs")), ("lamWOs", self._view("lamWOs")),
-                      ("ll", self._ll), ("lam", self.lam), ("u", self.u),
-                      ("step_betaU", self.steps["betaU"]), ("step_lamUz", self.steps["lamUz"]),
-                      ("step_lamWs", self.steps["lamWs"]), ("step_lamWOs", self.steps["lamWOs"]),
-                      ("acc", self._acc), ("lp", self._view("logPost")),
-                      ("scratch", self._scratch)):
-            if t.dtype != F64:
-                raise TypeError(f"mcmc state buffer {nm} must be float64")
-            setattr(S, nm, t.data_ptr())
-        if not self.u.is_contiguous() or self.u.shape != (self.C, self.nu):
-            raise TypeError("uniforms must be a contiguous (C, nu) block")
-        S.P, S.d = self.P, self.d
-        for i, nm in enumerate(ModelParams.names):
-            p = getattr(pr, nm)
-            S.dist[i] = _capi.MCMC_DIST[p.dist]
-            S.steptype[i] = _capi.MCMC_STEP[p.mcmcStepType]
-            S.pa[i], S.pb[i] = p.params
-            S.lo[i], S.hi[i] = p.bounds
-        return S
-
-    def _sweep(self) -> None:
-        """GPUSampler._sweep_fused with the gp_mcmc_ens_* calls and the sliced gp_loglik."""
-        self._S = self._state_struct()          # kept alive: the library reads it per call
-        S, T, C = ctypes.addressof(self._S), ctypes.addressof(self._T), self.C
-        stream = kernels._stream(self.dev)
-        last = len(self.groups) - 1
-        kinds = [ctypes.addressof(k) for k in self._kinds]
-        bufs = [self._gbuf[2 ** len(g) - 1] for g in self.groups]
-
-        def outs(b):
-            return b["beta"].data_ptr(), b["s"].data_ptr(), b["delta"].data_ptr()
-
-        _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[0], len(self.groups[0]), 1,
-                   *outs(bufs[0]), stream)
-        for gi, grp in enumerate(self.groups):
-            self._loglik(2 ** len(grp) - 1)
-            ll = bufs[gi]["ll"].data_ptr()
-            if gi == last or not self._merge:
-                _capi.call("gp_mcmc_ens_decide", S, T, C, kinds[gi], len(grp), int(gi == last),
-                           ll, stream)
-                if gi < last:
-                    _capi.call("gp_mcmc_ens_prep", S, T, C, kinds[gi + 1],
-                               len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]), stream)
-            else:
-                _capi.call("gp_mcmc_ens_step", S, T, C, kinds[gi], len(grp), 0, ll, S,
-                           kinds[gi + 1], len(self.groups[gi + 1]), 0, *outs(bufs[gi + 1]),
-                           stream)
-
-    def _capture(self) -> None:
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._sweep()
-        self.graph = g
-
-    def sweep(self) -> None:
-        if self.use_graph:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-        else:
-            self._sweep()
-
-    def _capture_block(self, record: bool) -> None:
-        """``block`` sweeps as one graph (GPUSampler._capture_block): sweep j reads the (C, nu)
-        uniforms of block row j and copies the flat states into record row j."""
-        B = self.block
-        if not hasattr(self, "_ublk"):
-            self._ublk = torch.zeros((B, self.C, self.nu), dtype=F64, device=self.dev)
-            self._rblk = torch.zeros((B,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        u0 = self.u
-        try:
-            with torch.cuda.graph(g):
-                for j in range(B):
-                    self.u = self._ublk[j]
-                    self._sweep()
-                    if record:
-                        self._rblk[j].copy_(self._flat)
-        finally:
-            self.u = u0
-        self._bgraph[record] = g
-
-    # -- chains --------------------------------------------------------------------------
     def run(self, nsamp: int, rngs: list, record: bool = True, block: int = 64):
         """``nsamp`` sweeps of every chain from the current states; chain c consumes
         ``rngs[c].random((rows, nu))`` block by block exactly as GPUSampler.run consumes its one
         generator.  Returns, when ``record``, the samples dict with a leading chain axis: betaU
         (C, N, (d+1) P), lamUz, lamWs (C, N, P), lamWOs, logPost (C, N, 1)."""
-        if len(rngs) != self.C:
-            raise ValueError(f"{len(rngs)} generators for {self.C} chains")
-        if self.st is None:
-            self.init_state()
-        if record:
-            rec = torch.empty((nsamp,) + tuple(self._flat.shape), dtype=F64, device=self.dev)
-        B = self.block if self.use_graph and self.block > 1 else 0
-        for a in range(0, nsamp, block):
-            b = min(nsamp, a + block)
-            U = self._t(np.stack([r.random((b - a, self.nu)) for r in rngs], axis=1))
-            i = a
-            while B and b - i >= B:                     # whole graph blocks
-                if record not in self._bgraph:
-                    self._capture_block(record)
-                self._ublk.copy_(U[i - a:i - a + B])
-                self._bgraph[record].replay()
-                if record:
-                    rec[i:i + B].copy_(self._rblk)
-                i += B
-            for i in range(i, b):                       # the rest one sweep at a time
-                self.u.copy_(U[i - a])
-                self.sweep()
-                if record:
-                    rec[i].copy_(self._flat)
-        for ws in self._ws.values():                    # one host check per run
-            ws.check_status()
-        if not record:
-            return None
-        rec = rec.cpu().numpy().transpose(1, 0, 2)
-        return {k: rec[:, :, a:b].copy() for k, (a, b) in self._cols.items()}
+        return self._run(nsamp, rngs, record, block)
 
 
 def tune_step_sizes_ensemble(sampler: EnsembleSampler, n_burn: int, n_levels: int,
                              rngs: list) -> None:
-    """tune_step_sizes over a whole ensemble: the same burn-in and ladder, every chain stepped
-    together, then the same per-element logistic fits per chain.  Updates each params[c]'s
-    mcmcStepParam, leaves the chains at the states reached, and sets ``sampler.last_tune`` to the
-    list of per-chain records."""
-    if sampler.st is None:
-        sampler.init_state()
-    ex = _ladder(n_levels)
-    bases = [{k: getattr(pr, k).mcmcStepParam.copy() for k in ModelParams.names}
-             for pr in sampler.params]
-    sampler.set_steps(1.0)
-    sampler.run(n_burn, rngs, record=False)
-    counts = []
-    for e in ex:
-        sampler.set_steps(2.0 ** e)
-        sampler.reset_counts()
-        sampler.run(n_burn, rngs, record=False)
-        counts.append(sampler.counts())
-    sampler.last_tune = []
-    for c, pr in enumerate(sampler.params):
-        new, info = _fit_chain_steps(pr, bases[c], ex, [lev[c] for lev in counts], n_burn)
-        for k in new:
-            getattr(pr, k).mcmcStepParam = new[k]
-        sampler.last_tune.append(info)
-    sampler.set_steps(1.0)
-    sampler.reset_counts()
+    """tune_step_sizes over a whole ensemble (_tune); ``sampler.last_tune`` is the list of
+    per-chain tune records."""
+    sampler.last_tune = _tune(sampler, n_burn, n_levels, rngs)
 
 
 # ------------------------------------------------------------------ convergence diagnostics

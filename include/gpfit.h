@@ -382,6 +382,10 @@ int gp_loglik_status(void* ws, int n, int batch, int reset, hipStream_t stream);
  *                        second group are its prep's codes - 10; S_next->P must equal S->P
  *                        (-18).
  * Single-workgroup launches (P <= 1024), stream-ordered, graph-capturable; 0 or < 0 (argument).
+ * Each of the three forwards to the gp_mcmc_ens_* call of the same name below with nchains = 1
+ * and zeroed strides: one set of kernels serves both families, and the return codes are that
+ * call's (-1 .. -7 for prep and decide, and for step also -11 .. -18; the ensemble-only -8, -9
+ * and -19 cannot occur with one chain).
  */
 #define GPFIT_MCMC_MAX_GROUP 4
 #define GPFIT_MCMC_GAMMA 0        /* (a - 1) log x - b x                                      */
@@ -420,14 +424,16 @@ int gp_mcmc_group_step(const gp_mcmc_state* S, const int* kinds, int g, int last
                        hipStream_t stream);
 
 /*
- * The same three steps for an ensemble of `nchains` chains that share X, P, d, the priors, the
+ * The three steps for an ensemble of `nchains` chains that share X, P, d, the priors, the
  * bounds and the step types (C repeat chains of one model, or C models on one design: equal or
- * different w_hat behind gp_loglik).  S describes chain 0; `strides` holds, for each pointer
+ * different w_hat behind gp_loglik): the kernels behind both families (gp_mcmc_group_* above
+ * forwards here with nchains = 1).  S describes chain 0; `strides` holds, for each pointer
  * field of gp_mcmc_state, the distance in doubles from one chain's buffer to the next chain's.
- * Workgroup c runs gp_mcmc_group_*'s code on chain c's buffers: the same arithmetic in the same
- * order (no FMA contraction, the in-order sums of lamWOs' decision and of lp), no atomics, and
+ * Workgroup c runs the step described above on chain c's buffers: a fixed arithmetic order per
+ * chain (no FMA contraction, the in-order sums of lamWOs' decision and of lp), no atomics, and
  * it touches no other chain's memory, so a chain's results do not depend on the other chains of
- * the call, and nchains = 1 gives gp_mcmc_group_*'s bits whatever the strides hold.
+ * the call: chain c's bits are those of a call with nchains = 1 on its buffers alone, whatever
+ * the strides of that call hold.
  * The batch is chain-major: chain c's rows of beta / s / delta / ll_all start at row
  * c (2^g - 1) P and are laid out within the chain as above, so any run of whole chains is one
  * contiguous gp_loglik batch (gp_mcmc_ens_step: ll_all with the decided group's g, beta / s /

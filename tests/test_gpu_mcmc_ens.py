@@ -75,7 +75,7 @@ def _references(dev, n, d, P, C, scale, nsw):
 
 @pytest.mark.parametrize("spec,graph", [(1, False), (2, True), (3, False), (3, True)])
 @pytest.mark.parametrize("n,d,P,C,scale", [(48, 2, 3, 3, 1.0), (48, 2, 1, 5, 1.0),
-                                           (130, 3, 2, 2, 0.3)])
+                                           (130, 3, 2, 2, 0.3), (48, 2, 3, 1, 1.0)])
 def test_chain_equals_lone_sampler_and_oracle(dev, n, d, P, C, scale, spec, graph):
     nsw = 25
     X, w, lam, lone, oracle = _references(dev, n, d, P, C, scale, nsw)
@@ -103,8 +103,17 @@ def test_chain_equals_lone_sampler_and_oracle(dev, n, d, P, C, scale, spec, grap
         np.testing.assert_array_equal(cnt[c]["lamWs"], acc["lamWs"])
         assert cnt[c]["lamWOs"][0] == acc["lamWOs"]
         assert acc["betaU"][1:].sum() > 0 and cnt[c]["lamUz"].sum() > 0
-    # chains differ from each other (different w_hat, starts and uniforms)
-    assert not np.allclose(rec["lamUz"][0], rec["lamUz"][1])
+    if C == 1:
+        # an ensemble of one and the lone sampler at the same spec issue the same calls
+        s, lrec = _lone(dev, X, w[0], lam[0], _params(d, P, C, scale)[0], 50, nsw,
+                        use_graph=graph, spec=spec)
+        for k in KEYS:
+            np.testing.assert_array_equal(rec[k][0], lrec[k], err_msg=k)
+        for k, v in s.counts().items():
+            np.testing.assert_array_equal(cnt[0][k], v, err_msg=str(k))
+    else:
+        # chains differ from each other (different w_hat, starts and uniforms)
+        assert not np.allclose(rec["lamUz"][0], rec["lamUz"][1])
     print(f"\nensemble vs lone sampler n={n} P={P} C={C} spec={spec} graph={graph}: "
           f"{'bit-exact' if exact else 'within 1e-12, not bit-exact'}")
 
