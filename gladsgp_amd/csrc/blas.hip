@@ -49,6 +49,12 @@ GP_DEV void stage_store(double* S, const double (&r)[16]) {
   }
 }
 
+// The C update of the general kernel and of both split-K reductions: alpha v + beta c with
+// beta c rounded first, and c not read at beta = 0 (it may hold NaN).
+GP_DEV void gemm_store(double* c, double v, double alpha, double beta) {
+  *c = (beta == 0.0) ? alpha * v : fma(alpha, v, beta * *c);
+}
+
 // opA(i,k): transa=0 -> A[i + k*lda] (NAT staging), 1 -> A[k + i*lda] (TRN staging)
 // opB(k,j): transb=0 -> B[k + j*ldb] (TRN staging), 1 -> B[j + k*ldb] (NAT staging)
 template <int TA, int TBT, typename EA, typename EB>
@@ -115,8 +121,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, int kchu
     if (part) {
       part[(long long)blockIdx.z * M * N + gi + (long long)gj * M] = v;
     } else {
-      double* c = C + gi + (long long)gj * ldc;
-      *c = (beta == 0.0) ? alpha * v : fma(alpha, v, beta * *c);
+      gemm_store(C + gi + (long long)gj * ldc, v, alpha, beta);
     }
   }
 }
@@ -129,8 +134,7 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ part, int splits
   const int gi = (int)(idx % M), gj = (int)(idx / M);
   double s = 0.0;
   for (int p = 0; p < splits; ++p) s += part[(long long)p * M * N + idx];
-  double* c = C + gi + (long long)gj * ldc;
-  *c = (beta == 0.0) ? alpha * s : fma(alpha, s, beta * *c);
+  gemm_store(C + gi + (long long)gj * ldc, s, alpha, beta);
 }
 
 // The tsk products' reduction (hundreds of slices over a small C: 256 x 512 x 25 at the fit):
@@ -161,8 +165,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(
 #pragma unroll
     for (int g = 1; g < kRedGroups; ++g) t += red[g][o];
     const int gi = (int)(idx % M), gj = (int)(idx / M);
-    double* c = C + gi + (long long)gj * ldc;
-    *c = (beta == 0.0) ? alpha * t : fma(alpha, t, beta * *c);
+    gemm_store(C + gi + (long long)gj * ldc, t, alpha, beta);
   }
 }
 
@@ -324,8 +327,8 @@ extern "C" int gp_mean_var(const double* x, long long N, int ddof, double* out, 
   hipLaunchKernelGGL(partial_sum_kernel, dim3(nb), dim3(256), 0, stream, x, N, out, work);
   hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, stream, work, nb,
                      1.0 / (double)(N - ddof), out + 1);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int gp_shift_diag(double* A, int r, int lda, double factor, hipStream_t stream) {
@@ -334,8 +337,8 @@ extern "C" int gp_shift_diag(double* A, int r, int lda, double factor, hipStream
   if (lda < r || lda < 1) return -3;
   if (r == 0) return 0;
   hipLaunchKernelGGL(shift_diag_kernel, dim3(1), dim3(256), 0, stream, A, r, lda, factor);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int gp_rowscale(double* M, int rows, int cols, int ld, const double* f, int inv,
@@ -349,8 +352,8 @@ extern "C" int gp_rowscale(double* M, int rows, int cols, int ld, const double* 
   const long long tot = (long long)rows * cols;
   hipLaunchKernelGGL(rowscale_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
                      M, rows, cols, ld, f, inv);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(hipGetLastError());
+  return 0;
 }
 
 namespace {
@@ -364,11 +367,18 @@ namespace {
 // the narrow side in registers / L2 and stream X with many loads in flight:
 //   tsk (C = X W, K = ny long, C small): every block owns one K-slice of kTskRows rows, each
 //       wave 64 rows (4 row tiles x 2 column tiles of 16 in MFMA accumulators).  X is loaded
-//       row-contiguous (8 lanes read 8 consecutive k of one row: 64 B per row, 8 rows per
-//       load), three K-groups ahead in registers, and transposed into the MFMA A layout through
-//       a wave-private LDS tile; partial C per slice, then splitk_reduce_wide_kernel (fixed order:
-//       deterministic).  (Round 5's first tsk loaded X straight into the A layout -- 16 rows x
-//       32 B per load -- and reached 0.19-0.25 of HBM: profiles/r05/r05g_prof_pca.log.)
+//       row-contiguous (8 lanes read one row's K-group, 8 rows per load), groups ahead in a
+//       register ring, and transposed into the MFMA A layout through a wave-private LDS tile;
+//       partial C per slice, then splitk_reduce_wide_kernel (fixed order: deterministic).
+//       gemm_tsk_kernel<EP, EW, V16> is the one kernel, in two forms that sum the same products
+//       in the same order (same bits):
+//         8-B form  (V16 = 0, any operand types): a lane loads one element, groups of 8 k (64 B
+//                   per row), X and W both three groups ahead;
+//         16-B form (V16 = 1, an fp64 X whose rows start 16-B aligned -- ts_vec_ok; the fit's
+//                   y_std is allocated with a padded row stride, emulator.py standardize_y): a
+//                   lane loads a pair, groups of 16 k (128 B per row), X two groups ahead, W one.
+//       (Round 5's first tsk loaded X straight into the A layout -- 16 rows x 32 B per load --
+//       and reached 0.19-0.25 of HBM: profiles/r05/r05g_prof_pca.log.)
 //   tsm (C = X^T Y or Q^T X, the big side is the output): every block owns kTsmRows rows of the
 //       big dimension and the whole K <= kTsmMaxK (the narrow operand read through L1 / L2),
 //       two blocks per CU; the accumulators go through LDS so the output is written as
@@ -388,95 +398,143 @@ constexpr int kTsMaxN = 32;          // narrow side (two 16-wide MFMA column til
 // K-groups (16 k each) in flight ahead of the one being multiplied (a ring of kTsRing register
 // buffers, indexed at compile time: the loops below are unrolled over the ring)
 constexpr int kTsRing = 3;    // tsm
-constexpr int kTskKG = 8;     // tsk: k per group (8 lanes read 64 contiguous bytes of a row)
-constexpr int kTskRing = 4;   // tsk: groups in registers, three in flight ahead
-constexpr int kTskPitch = 72; // tsk LDS transpose: doubles per k row of a wave's 64-row tile
+
+// The narrow operand W(k, j) = W[k*wk + j*wj] as one lane reads it: columns li and 16 + li of
+// the two MFMA column tiles.  c0 / c1 point at those columns clamped to N - 1 (N < 16 too): the
+// unmasked form then multiplies a finite column into C columns >= N that are never stored, and
+// every stored element sums the same products in the same order as the masked form (same bits).
+template <typename E>
+struct TsNarrow {
+  const E *c0, *c1;
+  long long wk;
+  bool ok0, ok1;     // the column itself is < N
+};
+
+template <typename E>
+GP_DEV TsNarrow<E> ts_narrow(const E* __restrict__ W, long long wk, long long wj, int li, int N) {
+  const int j0 = li, j1 = 16 + li;
+  return {W + (j0 < N ? j0 : N - 1) * wj, W + (j1 < N ? j1 : N - 1) * wj, wk, j0 < N, j1 < N};
+}
+
+// bb[u][0..1] = the lane's two columns of W at k + 4u, u < U.  FULL: no masks and one 64-bit
+// offset per group; otherwise zero at k + 4u >= ke and in columns >= N.
+template <bool FULL, int U, typename E>
+GP_DEV void ts_load_narrow(double (&bb)[U][2], const TsNarrow<E>& w, int k, int ke) {
+  if constexpr (FULL) {
+    const long long wo = (long long)k * w.wk, wk4 = 4LL * w.wk;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bb[u][0] = static_cast<double>(w.c0[wo + u * wk4]);
+      bb[u][1] = static_cast<double>(w.c1[wo + u * wk4]);
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int ku = k + 4 * u;
+      const bool ok = ku < ke;
+      bb[u][0] = (ok && w.ok0) ? static_cast<double>(w.c0[ku * w.wk]) : 0.0;
+      bb[u][1] = (ok && w.ok1) ? static_cast<double>(w.c1[ku * w.wk]) : 0.0;
+    }
+  }
+}
 
 // C(i, j) = sum_k P(i, k) W(k, j) for i < M (P(i,k) = P[k + i*ldp], contiguous in k), j < N <= 32,
 // W(k, j) = W[k*wk + j*wj], k in this block's slice; partial C to part[slice][j*M + i].
-template <typename EP, typename EW>
-__global__ __launch_bounds__(64 * kTskWaves, 8 / kTskWaves) void gemm_tsk_kernel(int M, int N, int K, int kslice,
-                                                          const EP* __restrict__ P, int ldp,
-                                                          const EW* __restrict__ W, long long wk,
-                                                          long long wj, double* __restrict__ part) {
-  constexpr int G = kTskKG, R = kTskRing, NQ = 64 * G / 64;   // NQ loads of one group per lane
-  __shared__ double xs[kTskWaves * G * kTskPitch];
+// A lane's load slot is (k offset EL c, row offset rr) = (lane & 7, lane >> 3): 8 lanes read
+// one row's G = 8 EL consecutive k, a load covers 8 rows, eight loads a wave's 64.
+template <typename EP, typename EW, bool V16>
+__global__ __launch_bounds__(64 * kTskWaves, 8 / kTskWaves) void gemm_tsk_kernel(
+    int M, int N, int K, int kslice, const EP* __restrict__ P, int ldp,
+    const EW* __restrict__ W, long long wk, long long wj, double* __restrict__ part) {
+  static_assert(!V16 || std::is_same<EP, double>::value, "the 16-B form loads fp64 pairs");
+  constexpr int EL = V16 ? 2 : 1;               // elements per lane and load
+  constexpr int G = 8 * EL;                     // k per group
+  constexpr int RX = V16 ? 3 : 4;               // X ring: loaded RX - 1 groups ahead
+  constexpr int RW = V16 ? 2 : 4;               // W ring: loaded RW - 1 groups ahead
+  constexpr int UN = V16 ? 6 : 4;               // lcm(RX, RW): the unrolled ring
+  constexpr int PITCH = V16 ? 68 : 72;          // LDS transpose: doubles per k row of a wave's tile
+  using XV = std::conditional_t<V16, double2, double>;
+  __shared__ double xs[kTskWaves * G * PITCH];
   const int slice = blockIdx.x, rg = blockIdx.y;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int li = lane & 15, ks = lane >> 4;
-  const int kk = lane % G, rr = lane / G;                // load slot: k offset, row offset
+  const int c = lane & 7, rr = lane >> 3;
   const int kb = slice * kslice, ke = min(K, kb + kslice);
   const int row0 = rg * kTskRows + w * 64;
-  double* xw = xs + w * G * kTskPitch;
+  double* xw = xs + w * G * PITCH;
   f64x4 acc[4][2];
 #pragma unroll
   for (int t = 0; t < 4; ++t) acc[t][0] = acc[t][1] = zero4();
-  // load q of a group: row row0 + (64 / G) q + rr, k = k0 + kk; rows >= M masked (never read)
-  constexpr int RS = 64 / G;
-  const EP* lrow = P + (long long)(row0 + rr) * ldp + kk;
-  const long long qstep = (long long)RS * ldp;
-  const int jc0 = li, jc1 = 16 + li;
-  // FULL: the unmasked fast path of tsk16 / tsm (rows < M, whole groups; same bits)
-  const int jc0c = jc0 < N ? jc0 : N - 1, jc1c = jc1 < N ? jc1 : N - 1;   // N < 16 too
-  const EW* const wc0 = W + jc0c * wj;
-  const EW* const wc1 = W + jc1c * wj;
-  const long long wk4 = 4LL * wk;
-  double xr[R][NQ], bv[R][G / 4][2];
+  // load q of a group: row row0 + 8 q + rr, k = k0 + EL c (+ 1); rows >= M masked (never read)
+  const EP* lrow = P + (long long)(row0 + rr) * ldp + EL * c;
+  const long long qstep = 8LL * ldp;
+  const TsNarrow<EW> wn = ts_narrow(W, wk, wj, li, N);
+  XV xr[RX][8];
+  double bv[RW][G / 4][2];
+  // FULL (the block's rows < M and its k range whole groups: all but a product's last slice):
+  // loads without per-lane masks and one 64-bit multiply per W group, as in tsm (the masked
+  // form spent more instructions on exec-mask branches and 64-bit address arithmetic than on
+  // MFMAs: profiles/r05/r05_pmc_ts.txt, MFMA busy 0.49).
   auto run = [&](auto fullc) {
     constexpr bool FULL = decltype(fullc)::value;
-    auto load = [&](double (&xb)[NQ], double (&bb)[G / 4][2], int k0) {
-      if constexpr (FULL) {
-        const EP* lk = lrow + k0;
+    auto load_x = [&](XV (&xb)[8], int k0) {
+      const EP* lk = lrow + k0;
+      const int k = k0 + EL * c;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) xb[q] = static_cast<double>(lk[q * qstep]);
-        const long long wo = (long long)(k0 + ks) * wk;
-#pragma unroll
-        for (int u = 0; u < G / 4; ++u) {
-          bb[u][0] = static_cast<double>(wc0[wo + u * wk4]);
-          bb[u][1] = static_cast<double>(wc1[wo + u * wk4]);
-        }
-      } else {
-        const bool kok = k0 + kk < ke;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          xb[q] = (kok && row0 + RS * q + rr < M) ? static_cast<double>(lrow[q * qstep + k0])
-                                                   : 0.0;
-#pragma unroll
-        for (int u = 0; u < G / 4; ++u) {
-          const int k = k0 + 4 * u + ks;
-          const bool ok = k < ke;
-          bb[u][0] = (ok && jc0 < N) ? static_cast<double>(W[k * wk + jc0 * wj]) : 0.0;
-          bb[u][1] = (ok && jc1 < N) ? static_cast<double>(W[k * wk + jc1 * wj]) : 0.0;
+      for (int q = 0; q < 8; ++q) {
+        const bool ok = FULL || (k < ke && row0 + 8 * q + rr < M);
+        if constexpr (V16) {
+          // (k even < ke: the pair's second element is inside the padded row; zeroed past ke)
+          double2 v = make_double2(0.0, 0.0);
+          if (ok) v = *reinterpret_cast<const double2*>(lk + q * qstep);
+          if (!FULL && k + 1 >= ke) v.y = 0.0;
+          xb[q] = v;
+        } else {
+          xb[q] = ok ? static_cast<double>(lk[q * qstep]) : 0.0;
         }
       }
     };
+    auto load_w = [&](double (&bb)[G / 4][2], int k0) {
+      ts_load_narrow<FULL>(bb, wn, k0 + ks, ke);
+    };
     // prologue: only groups inside the slice (FULL loads are unmasked: a group at or past ke
     // would read up to 16 k past the slice, i.e. past X's last row and W's last k)
-#pragma unroll
-    for (int q = 0; q < R - 1; ++q)
-      if (kb + G * q < ke) load(xr[q], bv[q], kb + G * q);
-    for (int k0 = kb; k0 < ke; k0 += G * R) {
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
+    static_for<0, (RX > RW ? RX : RW) - 1, 1>([&](auto Q) {
+      constexpr int q = decltype(Q)::value;
+      if (kb + G * q < ke) {
+        if constexpr (q < RX - 1) load_x(xr[q], kb + G * q);
+        if constexpr (q < RW - 1) load_w(bv[q], kb + G * q);
+      }
+    });
+    for (int k0 = kb; k0 < ke; k0 += G * UN) {
+      static_for<0, UN, 1>([&](auto Q) {
+        constexpr int q = decltype(Q)::value;
         const int kq = k0 + G * q;
-        if (kq >= ke) break;
-        const int kn = kq + G * (R - 1);                    // the group R - 1 ahead
-        if (kn < ke) load(xr[(q + R - 1) % R], bv[(q + R - 1) % R], kn);
+        if (kq >= ke) return;
+        if (kq + G * (RX - 1) < ke) load_x(xr[(q + RX - 1) % RX], kq + G * (RX - 1));
+        if (kq + G * (RW - 1) < ke) load_w(bv[(q + RW - 1) % RW], kq + G * (RW - 1));
         // transpose: xw[k][row] (one wave's LDS: its own DS instructions run in order)
 #pragma unroll
-        for (int i = 0; i < NQ; ++i) xw[kk * kTskPitch + RS * i + rr] = xr[q][i];
+        for (int i = 0; i < 8; ++i) {
+          if constexpr (V16) {
+            xw[(2 * c) * PITCH + 8 * i + rr] = xr[q % RX][i].x;
+            xw[(2 * c + 1) * PITCH + 8 * i + rr] = xr[q % RX][i].y;
+          } else {
+            xw[c * PITCH + 8 * i + rr] = xr[q % RX][i];
+          }
+        }
 #pragma unroll
         for (int u = 0; u < G / 4; ++u) {
           double a[4];
 #pragma unroll
-          for (int t = 0; t < 4; ++t) a[t] = xw[(4 * u + ks) * kTskPitch + 16 * t + li];
+          for (int t = 0; t < 4; ++t) a[t] = xw[(4 * u + ks) * PITCH + 16 * t + li];
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            acc[t][0] = mfma16x16x4(a[t], bv[q][u][0], acc[t][0]);
-            acc[t][1] = mfma16x16x4(a[t], bv[q][u][1], acc[t][1]);
+            acc[t][0] = mfma16x16x4(a[t], bv[q % RW][u][0], acc[t][0]);
+            acc[t][1] = mfma16x16x4(a[t], bv[q % RW][u][1], acc[t][1]);
           }
         }
-      }
+      });
     }
   };
   if (rg * kTskRows + kTskRows <= M && (ke - kb) % G == 0) run(std::true_type{});
@@ -522,45 +580,33 @@ __global__ __launch_bounds__(256, kTsmOcc) void gemm_tsm_kernel(int M, int N, in
     rok[t] = r < M;
     pcol[t] = P + (rok[t] ? r : 0);
   }
-  const int jc0 = li, jc1 = 16 + li;
   // K-group of 16: lane (row li, slot ks) holds k = k0 + 4u + ks of its 4 row tiles.
   // FULL (every block row < M and K % 16 == 0, i.e. all but a product's last block): no
   // per-load masks and one 64-bit address per (group, u) -- the masked form's per-load
   // exec-mask branches and 64-bit multiplies outnumbered its MFMAs (r05_pmc_ts.txt: MFMA busy
-  // 0.46 with waves waiting only 19% of their cycles).  Columns >= N then multiply a clamped,
-  // finite column of Q into C columns that are never stored; every stored element sums the
-  // same products in the same order, so the results are the masked form's bits.
-  const int jc0c = jc0 < N ? jc0 : N - 1, jc1c = jc1 < N ? jc1 : N - 1;   // N < 16 too
-  const long long ldp4 = 4LL * ldp, qk4 = 4LL * qk;
-  const EQ* const qc0 = Q + jc0c * qj;
-  const EQ* const qc1 = Q + jc1c * qj;
+  // 0.46 with waves waiting only 19% of their cycles).
+  const long long ldp4 = 4LL * ldp;
+  const TsNarrow<EQ> qn = ts_narrow(Q, qk, qj, li, N);
   double a[kTsRing][T][4], bv[kTsRing][4][2];
   auto run = [&](auto fullc) {
     constexpr bool FULL = decltype(fullc)::value;
     auto load = [&](double (&ab)[T][4], double (&bb)[4][2], int k0) {
       if constexpr (FULL) {
         const EP* pk = P + rbase + li + (long long)(k0 + ks) * ldp;
-        const long long qo = (long long)(k0 + ks) * qk;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const EP* pu = pk + u * ldp4;
+        for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int t = 0; t < T; ++t) ab[t][u] = static_cast<double>(pu[16 * t]);
-          bb[u][0] = static_cast<double>(qc0[qo + u * qk4]);
-          bb[u][1] = static_cast<double>(qc1[qo + u * qk4]);
-        }
+          for (int t = 0; t < T; ++t) ab[t][u] = static_cast<double>(pk[u * ldp4 + 16 * t]);
       } else {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int k = k0 + 4 * u + ks;
-          const bool kok = k < K;
 #pragma unroll
           for (int t = 0; t < T; ++t)
-            ab[t][u] = (kok && rok[t]) ? static_cast<double>(pcol[t][(long long)k * ldp]) : 0.0;
-          bb[u][0] = (kok && jc0 < N) ? static_cast<double>(Q[k * qk + jc0 * qj]) : 0.0;
-          bb[u][1] = (kok && jc1 < N) ? static_cast<double>(Q[k * qk + jc1 * qj]) : 0.0;
+            ab[t][u] = (k < K && rok[t]) ? static_cast<double>(pcol[t][(long long)k * ldp]) : 0.0;
         }
       }
+      ts_load_narrow<FULL>(bb, qn, k0 + ks, K);
     };
     // prologue: only groups < K (FULL loads are unmasked; K = 16 would otherwise read P's
     // columns and Q's rows 16..31, past both operands)
@@ -594,6 +640,8 @@ __global__ __launch_bounds__(256, kTsmOcc) void gemm_tsm_kernel(int M, int N, in
       for (int q = 0; q < 4; ++q)
         cs[(w * 16 * T + 16 * t + ks + 4 * q) * 33 + 16 * jt + li] = acc[t][jt][q];
   __syncthreads();
+  // not gemm_store: this kernel has always rounded alpha v first and then fused beta c into it;
+  // the general kernel rounds beta c first.  Merging the two would change the bits of one.
   const int rows = (int)min((long long)kTsmRows, M - i0);
   if (cj == 1) {                                // C(i, j) runs along j: rows of N doubles
     for (int e = threadIdx.x; e < rows * N; e += 256) {
@@ -612,126 +660,6 @@ __global__ __launch_bounds__(256, kTsmOcc) void gemm_tsm_kernel(int M, int N, in
   }
 }
 
-// ---- 16-byte form for fp64 ensembles whose rows start 16-B aligned (the fit's y_std is
-// allocated with a padded row stride, emulator.py standardize_y) -------------------------------
-// tsk16: as gemm_tsk_kernel, but 8 lanes read one row's 16 k as 16-B pairs (128 B per row, 8 rows
-// per load; 64 B with 8-B loads); X three groups ahead, W two (a 6-group unrolled ring).
-constexpr int kTsk16Pitch = 68;
-
-template <typename EW>
-__global__ __launch_bounds__(64 * kTskWaves, 8 / kTskWaves) void gemm_tsk16_kernel(int M, int N, int K, int kslice,
-                                                            const double* __restrict__ P, int ldp,
-                                                            const EW* __restrict__ W, long long wk,
-                                                            long long wj,
-                                                            double* __restrict__ part) {
-  constexpr int G = 16, RX = 3, RW = 2;
-  __shared__ double xs[kTskWaves * G * kTsk16Pitch];
-  const int slice = blockIdx.x, rg = blockIdx.y;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int li = lane & 15, ks = lane >> 4;
-  const int c = lane & 7, rr = lane >> 3;                // load slot: k pair 2c, row offset rr
-  const int kb = slice * kslice, ke = min(K, kb + kslice);
-  const int row0 = rg * kTskRows + w * 64;
-  double* xw = xs + w * G * kTsk16Pitch;
-  f64x4 acc[4][2];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t][0] = acc[t][1] = zero4();
-  const double* lrow = P + (long long)(row0 + rr) * ldp + 2 * c;
-  const long long qstep = 8LL * ldp;
-  const int jc0 = li, jc1 = 16 + li;
-  // FULL (the block's rows < M and its k range whole groups of 16: all but a product's last
-  // slice): loads without per-lane masks and one 64-bit multiply per W group, as in tsm
-  // (the masked form spent more instructions on exec-mask branches and 64-bit address
-  // arithmetic than on MFMAs: profiles/r05/r05_pmc_ts.txt, MFMA busy 0.49).  Columns >= N
-  // read a clamped, finite column of W into C columns that are never stored: same bits.
-  const int jc0c = jc0 < N ? jc0 : N - 1, jc1c = jc1 < N ? jc1 : N - 1;   // N < 16 too
-  const EW* const wc0 = W + jc0c * wj;
-  const EW* const wc1 = W + jc1c * wj;
-  const long long wk4 = 4LL * wk;
-  double2 xr[RX][8];
-  double bv[RW][4][2];
-  auto run = [&](auto fullc) {
-    constexpr bool FULL = decltype(fullc)::value;
-    // (k0 + 2c even < ke: the pair's second element is inside the padded row; zeroed past ke)
-    auto load_x = [&](double2 (&xb)[8], int k0) {
-      if constexpr (FULL) {
-        const double* lk = lrow + k0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) xb[q] = *reinterpret_cast<const double2*>(lk + q * qstep);
-      } else {
-        const int k = k0 + 2 * c;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          double2 v = make_double2(0.0, 0.0);
-          if (k < ke && row0 + 8 * q + rr < M)
-            v = *reinterpret_cast<const double2*>(lrow + q * qstep + k0);
-          if (k + 1 >= ke) v.y = 0.0;
-          xb[q] = v;
-        }
-      }
-    };
-    auto load_w = [&](double (&bb)[4][2], int k0) {
-      if constexpr (FULL) {
-        const long long wo = (long long)(k0 + ks) * wk;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          bb[u][0] = static_cast<double>(wc0[wo + u * wk4]);
-          bb[u][1] = static_cast<double>(wc1[wo + u * wk4]);
-        }
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int k = k0 + 4 * u + ks;
-          const bool ok = k < ke;
-          bb[u][0] = (ok && jc0 < N) ? static_cast<double>(W[k * wk + jc0 * wj]) : 0.0;
-          bb[u][1] = (ok && jc1 < N) ? static_cast<double>(W[k * wk + jc1 * wj]) : 0.0;
-        }
-      }
-    };
-    load_x(xr[0], kb);
-    load_w(bv[0], kb);
-    if (kb + G < ke) load_x(xr[1], kb + G);      // a 16-long slice has no second group
-    for (int k0 = kb; k0 < ke; k0 += G * RX * RW) {
-      static_for<0, RX * RW, 1>([&](auto Q) {
-        constexpr int q = decltype(Q)::value;
-        const int kq = k0 + G * q;
-        if (kq >= ke) return;
-        if (kq + 2 * G < ke) load_x(xr[(q + 2) % RX], kq + 2 * G);
-        if (kq + G < ke) load_w(bv[(q + 1) % RW], kq + G);
-        // transpose: xw[k][row] (one wave's LDS: its own DS instructions run in order)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          xw[(2 * c) * kTsk16Pitch + 8 * i + rr] = xr[q % RX][i].x;
-          xw[(2 * c + 1) * kTsk16Pitch + 8 * i + rr] = xr[q % RX][i].y;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          double a[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) a[t] = xw[(4 * u + ks) * kTsk16Pitch + 16 * t + li];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            acc[t][0] = mfma16x16x4(a[t], bv[q % RW][u][0], acc[t][0]);
-            acc[t][1] = mfma16x16x4(a[t], bv[q % RW][u][1], acc[t][1]);
-          }
-        }
-      });
-    }
-  };
-  if (rg * kTskRows + kTskRows <= M && (ke - kb) % G == 0) run(std::true_type{});
-  else run(std::false_type{});
-  double* pp = part + (long long)slice * M * N;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = row0 + 16 * t + ks + 4 * q, j = 16 * jt + li;
-        if (r < M && j < N) pp[(long long)j * M + r] = acc[t][jt][q];
-      }
-}
-
 // The 16-B form applies to an fp64 big operand with a 16-B aligned base and an even leading
 // dimension (a pair never reads past the row: an even ldp >= len rounds len up inside it).
 // (A 16-B tsm, each lane reading rows 2i, 2i + 1 of a column, ran 2.4 vs 1.6 ms on the fit's
@@ -742,101 +670,126 @@ bool ts_vec_ok(const E* p, int ld, int len) {
          ld >= ((len + 1) & ~1);
 }
 
-// Which tall-skinny kernel serves (transa, transb, m, n, k), if any:
-//   1 tsk: transa = 1 (A's columns are C's rows), n <= 32, k >= kTskMinK;
-//   2 tsm: transa = 0, n <= 32, k <= kTsmMaxK, m >= 8192 (the big side is C's rows);
-//   3 tsm on the transpose: transb = 1, m <= 32, k <= kTsmMaxK, n >= 8192 (C^T's rows).
-int ts_kind(int transa, int transb, int m, int n, int k) {
-  if (transa == 1 && n <= kTsMaxN && k >= kTskMinK) return 1;
-  if (transa == 0 && n <= kTsMaxN && k <= kTsmMaxK && m >= 8192) return 2;
-  if (transb == 1 && m <= kTsMaxN && k <= kTsmMaxK && n >= 8192) return 3;
-  return 0;
+// How one product runs: which kernel, over how many K ranges, and the workspace that takes.
+// Filled from (transa, transb, m, n, k) alone, so the size query and the launch cannot differ.
+enum GemmKind {
+  kGeneral,   // gemm_kernel, split-K over `splits` chunks of kchunk (one chunk: no workspace)
+  kTsk,       // transa = 1 (A's columns are C's rows), n <= 32, k >= kTskMinK: `splits` slices
+  kTsm,       // transa = 0, n <= 32, k <= kTsmMaxK, m >= 8192 (the big side is C's rows)
+  kTsmT,      // tsm on the transpose: transb = 1, m <= 32, k <= kTsmMaxK, n >= 8192 (C^T's rows)
+};
+struct GemmPlan {
+  GemmKind kind;
+  int splits, kchunk;   // K ranges (grid.z chunks or tsk slices) and the length of one
+  int groups;           // tsk: row groups of kTskRows
+  long long ws_bytes;   // partial slabs; 0: the product needs no workspace
+};
+
+GemmPlan plan_general(int m, int n, int k, bool split) {
+  GemmPlan p = {kGeneral, 1, TB, 0, 0};
+  if (k <= 0) return p;
+  const int s = split ? choose_splits(m, n, k) : 1;
+  p.kchunk = gp_ceil_div(gp_ceil_div(k, s), TB) * TB;
+  p.splits = gp_ceil_div(k, p.kchunk);
+  if (s > 1) p.ws_bytes = (long long)s * m * n * 8;
+  return p;
 }
 
-// tsk's K slices: eight waves per CU over all row groups, each slice a multiple of 16.
-void tsk_shape(int m, int k, int& groups, int& slices, int& kslice) {
-  groups = gp_ceil_div(m, kTskRows);
-  slices = max(1, (2048 / kTskWaves) / groups);
-  kslice = gp_ceil_div(gp_ceil_div(k, slices), 16) * 16;
-  slices = gp_ceil_div(k, kslice);
-}
-
-}  // namespace
-
-extern "C" long long gp_dgemm_ws_bytes(int m, int n, int k) {
-  if (m <= 0 || n <= 0 || k <= 0) return 0;
-  const int s = choose_splits(m, n, k);
-  long long bytes = s > 1 ? (long long)s * m * n * 8 : 0;
-  if (n <= kTsMaxN && k >= kTskMinK) {            // a tsk product (transa = 1)
-    int g, sl, kc;
-    tsk_shape(m, k, g, sl, kc);
-    bytes = max(bytes, (long long)sl * m * n * 8);
+GemmPlan gemm_plan(int transa, int transb, int m, int n, int k) {
+  if (transa == 1 && n <= kTsMaxN && k >= kTskMinK) {
+    // K slices: eight waves per CU over all row groups, each slice a multiple of 16
+    GemmPlan p = {kTsk, 0, 0, gp_ceil_div(m, kTskRows), 0};
+    p.kchunk = gp_ceil_div(gp_ceil_div(k, max(1, (2048 / kTskWaves) / p.groups)), 16) * 16;
+    p.splits = gp_ceil_div(k, p.kchunk);
+    p.ws_bytes = (long long)p.splits * m * n * 8;
+    return p;
   }
-  return bytes;
+  if (k > 0 && k <= kTsmMaxK) {
+    if (transa == 0 && n <= kTsMaxN && m >= 8192) return {kTsm, 1, k, 0, 0};
+    if (transb == 1 && m <= kTsMaxN && n >= 8192) return {kTsmT, 1, k, 0, 0};
+  }
+  return plan_general(m, n, k, true);
 }
 
-namespace {
+// f(EA{}, EB{}) with the element types that (a_f32, b_f32) name
+template <class F>
+void with_elem_types(int a_f32, int b_f32, F&& f) {
+  if (a_f32 && b_f32) f(float{}, float{});
+  else if (a_f32) f(float{}, double{});
+  else if (b_f32) f(double{}, float{});
+  else f(double{}, double{});
+}
+
+struct GemmArgs {
+  int transa, transb, m, n, k;
+  double alpha;
+  const void* A;
+  int lda;
+  const void* B;
+  int ldb;
+  double beta;
+  double* C;
+  int ldc;
+  double* part;
+  hipStream_t stream;
+};
+
 template <typename EA, typename EB>
-hipError_t launch_ts(int kind, int transa, int transb, int m, int n, int k, double alpha,
-                            const void* A, int lda, const void* B, int ldb, double beta,
-                            double* C, int ldc, double* part, hipStream_t stream) {
-  const EA* a = static_cast<const EA*>(A);
-  const EB* b = static_cast<const EB*>(B);
-  if (kind == 1) {
-    int groups, slices, kslice;
-    tsk_shape(m, k, groups, slices, kslice);
+hipError_t launch_gemm(const GemmPlan& p, const GemmArgs& g) {
+  const EA* a = static_cast<const EA*>(g.A);
+  const EB* b = static_cast<const EB*>(g.B);
+  const int m = g.m, n = g.n, k = g.k;
+  const long long tot = (long long)m * n;
+  if (p.kind == kTsk) {
     // W(k, j) = opB(k, j): transb 0 -> B[k + j*ldb], 1 -> B[j + k*ldb]
-    const long long wk = transb ? ldb : 1, wj = transb ? 1 : ldb;
-    if constexpr (sizeof(EA) == 8) {
-      if (ts_vec_ok(a, lda, k))
-        hipLaunchKernelGGL((gemm_tsk16_kernel<EB>), dim3(slices, groups), dim3(64 * kTskWaves), 0, stream,
-                           m, n, k, kslice, reinterpret_cast<const double*>(a), lda, b, wk, wj,
-                           part);
-      else
-        hipLaunchKernelGGL((gemm_tsk_kernel<EA, EB>), dim3(slices, groups), dim3(64 * kTskWaves), 0, stream,
-                           m, n, k, kslice, a, lda, b, wk, wj, part);
-    } else {
-      hipLaunchKernelGGL((gemm_tsk_kernel<EA, EB>), dim3(slices, groups), dim3(64 * kTskWaves), 0, stream, m,
-                         n, k, kslice, a, lda, b, wk, wj, part);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const long long tot = (long long)m * n;
+    const long long wk = g.transb ? g.ldb : 1, wj = g.transb ? 1 : g.ldb;
+    constexpr bool can16 = sizeof(EA) == 8;
+    auto kern = (can16 && ts_vec_ok(a, g.lda, k)) ? gemm_tsk_kernel<EA, EB, can16>
+                                                  : gemm_tsk_kernel<EA, EB, false>;
+    hipLaunchKernelGGL(kern, dim3(p.splits, p.groups), dim3(64 * kTskWaves), 0, g.stream, m, n, k,
+                       p.kchunk, a, g.lda, b, wk, wj, g.part);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)((tot + 31) / 32)), dim3(256), 0,
-                       stream, part, slices, m, n, alpha, beta, C, ldc);
-    return hipGetLastError();
-  }
-  if (kind == 2) {
+                       g.stream, g.part, p.splits, m, n, g.alpha, g.beta, g.C, g.ldc);
+  } else if (p.kind == kTsm) {
     // C(i, j) = sum_k A[i + k*lda] opB(k, j), C[i + j*ldc]
-    const long long qk = transb ? ldb : 1, qj = transb ? 1 : ldb;
+    const long long qk = g.transb ? g.ldb : 1, qj = g.transb ? 1 : g.ldb;
     hipLaunchKernelGGL((gemm_tsm_kernel<EA, EB>), dim3(gp_ceil_div(m, kTsmRows)), dim3(256), 0,
-                       stream, m, n, k, a, lda, b, qk, qj, alpha, beta, C, 1LL, (long long)ldc);
-  } else {
+                       g.stream, m, n, k, a, g.lda, b, qk, qj, g.alpha, g.beta, g.C, 1LL,
+                       (long long)g.ldc);
+  } else if (p.kind == kTsmT) {
     // C^T(j, i) = sum_k B[j + k*ldb] opA(i, k), C[i + j*ldc]: the big operand is B
-    const long long qk = transa ? 1 : lda, qj = transa ? lda : 1;
+    const long long qk = g.transa ? 1 : g.lda, qj = g.transa ? g.lda : 1;
     hipLaunchKernelGGL((gemm_tsm_kernel<EB, EA>), dim3(gp_ceil_div(n, kTsmRows)), dim3(256), 0,
-                       stream, n, m, k, b, ldb, a, qk, qj, alpha, beta, C, (long long)ldc, 1LL);
+                       g.stream, n, m, k, b, g.ldb, a, qk, qj, g.alpha, g.beta, g.C,
+                       (long long)g.ldc, 1LL);
+  } else {
+    double* part = p.splits > 1 ? g.part : nullptr;
+    const dim3 grid(gp_ceil_div(m, TB) * gp_ceil_div(n, TB), 1, p.splits);
+#define GP_GEMM(TA_, TB_)                                                                     \
+  hipLaunchKernelGGL((gemm_kernel<TA_, TB_, EA, EB>), grid, dim3(256), 0, g.stream, m, n, k,   \
+                     p.kchunk, a, g.lda, b, g.ldb, g.alpha, g.beta, g.C, g.ldc, part)
+    if (g.transa == 0 && g.transb == 0) GP_GEMM(0, 0);
+    else if (g.transa == 0 && g.transb == 1) GP_GEMM(0, 1);
+    else if (g.transa == 1 && g.transb == 0) GP_GEMM(1, 0);
+    else GP_GEMM(1, 1);
+#undef GP_GEMM
+    if (!part) return hipGetLastError();
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
+                       g.stream, part, p.splits, m, n, g.alpha, g.beta, g.C, g.ldc);
   }
   return hipGetLastError();
 }
 
-template <typename EA, typename EB>
-static void launch_gemm(int transa, int transb, dim3 grid, hipStream_t stream, int m, int n,
-                        int k, int kchunk, const void* A, int lda, const void* B, int ldb,
-                        double alpha, double beta, double* C, int ldc, double* part) {
-  const EA* a = static_cast<const EA*>(A);
-  const EB* b = static_cast<const EB*>(B);
-#define GP_GEMM(TA_, TB_)                                                                     \
-  hipLaunchKernelGGL((gemm_kernel<TA_, TB_, EA, EB>), grid, dim3(256), 0, stream, m, n, k,     \
-                     kchunk, a, lda, b, ldb, alpha, beta, C, ldc, part)
-  if (transa == 0 && transb == 0) GP_GEMM(0, 0);
-  else if (transa == 0 && transb == 1) GP_GEMM(0, 1);
-  else if (transa == 1 && transb == 0) GP_GEMM(1, 0);
-  else GP_GEMM(1, 1);
-#undef GP_GEMM
-}
-
 }  // namespace
+
+// The largest need over the plans a product of this size can be given: the general kernel's
+// split-K (any trans pair, and what a tsk product falls back to) and tsk's slices (transa = 1).
+extern "C" long long gp_dgemm_ws_bytes(int m, int n, int k) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  return max(plan_general(m, n, k, true).ws_bytes, gemm_plan(1, 0, m, n, k).ws_bytes);
+}
 
 extern "C" int gp_gemm_ex(int transa, int transb, int m, int n, int k, double alpha,
                           const void* A, int a_f32, int lda, const void* B, int b_f32, int ldb,
@@ -856,59 +809,18 @@ extern "C" int gp_gemm_ex(int transa, int transb, int m, int n, int k, double al
   if (!C) return -14;
   if (ldc < m || ldc < 1) return -15;
   if (m == 0 || n == 0) return 0;
-  const int tk = (k > 0) ? ts_kind(transa, transb, m, n, k) : 0;
-  if (tk) {
-    long long need = 0;
-    if (tk == 1) {
-      int g, sl, kc;
-      tsk_shape(m, k, g, sl, kc);
-      need = (long long)sl * m * n * 8;
-    }
-    if (tk != 1 || (ws && ws_bytes >= need)) {
-      hipError_t e;
-      double* part = static_cast<double*>(ws);
-      if (a_f32 && b_f32)
-        e = launch_ts<float, float>(tk, transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C,
-                                    ldc, part, stream);
-      else if (a_f32)
-        e = launch_ts<float, double>(tk, transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C,
-                                     ldc, part, stream);
-      else if (b_f32)
-        e = launch_ts<double, float>(tk, transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C,
-                                     ldc, part, stream);
-      else
-        e = launch_ts<double, double>(tk, transa, transb, m, n, k, alpha, A, lda, B, ldb, beta,
-                                      C, ldc, part, stream);
-      return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
-    }
-  }
-  int splits = (k > 0) ? choose_splits(m, n, k) : 1;
-  if (splits > 1 && (!ws || ws_bytes < (long long)splits * m * n * 8)) splits = 1;
-  const int kchunk = (k > 0) ? gp_ceil_div(gp_ceil_div(k, splits), TB) * TB : TB;
-  splits = (k > 0) ? gp_ceil_div(k, kchunk) : 1;
-  double* part = (splits > 1) ? static_cast<double*>(ws) : nullptr;
-  dim3 grid(gp_ceil_div(m, TB) * gp_ceil_div(n, TB), 1, splits);
-  if (a_f32 && b_f32)
-    launch_gemm<float, float>(transa, transb, grid, stream, m, n, k, kchunk, A, lda, B, ldb,
-                              alpha, beta, C, ldc, part);
-  else if (a_f32)
-    launch_gemm<float, double>(transa, transb, grid, stream, m, n, k, kchunk, A, lda, B, ldb,
-                               alpha, beta, C, ldc, part);
-  else if (b_f32)
-    launch_gemm<double, float>(transa, transb, grid, stream, m, n, k, kchunk, A, lda, B, ldb,
-                               alpha, beta, C, ldc, part);
-  else
-    launch_gemm<double, double>(transa, transb, grid, stream, m, n, k, kchunk, A, lda, B, ldb,
-                                alpha, beta, C, ldc, part);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
-  if (part) {
-    const long long tot = (long long)m * n;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                       stream, part, splits, m, n, alpha, beta, C, ldc);
-    e = hipGetLastError();
-    if (e != hipSuccess) return GPFIT_ERR_HIP - (int)e;
-  }
+  // without the workspace its plan needs, a tsk product runs as general GEMM and split-K unsplit
+  auto fits = [&](const GemmPlan& p) { return p.ws_bytes == 0 || (ws && ws_bytes >= p.ws_bytes); };
+  GemmPlan p = gemm_plan(transa, transb, m, n, k);
+  if (p.kind == kTsk && !fits(p)) p = plan_general(m, n, k, true);
+  if (!fits(p)) p = plan_general(m, n, k, false);
+  const GemmArgs g = {transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc,
+                      static_cast<double*>(ws), stream};
+  hipError_t e = hipSuccess;
+  with_elem_types(a_f32, b_f32, [&](auto ea, auto eb) {
+    e = launch_gemm<decltype(ea), decltype(eb)>(p, g);
+  });
+  GP_CK(e);
   return 0;
 }
 
@@ -937,8 +849,8 @@ extern "C" int gp_sim_stats(const double* Y, int n, int ny, long long ldy, doubl
   else
     hipLaunchKernelGGL(simstats_kernel, dim3(gp_ceil_div(ny, 256)), dim3(256), 0, stream, Y, n,
                        ny, ldy, sd_floor, mu, sd);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int gp_standardize(const double* Y, int n, int ny, long long ldy, const double* mu,
@@ -956,6 +868,6 @@ extern "C" int gp_standardize(const double* Y, int n, int ny, long long ldy, con
   const long long tot = (long long)n * ny;
   hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
                      stream, Y, n, ny, ldy, mu, sd, out, ldo, inverse);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
+  GP_CK(hipGetLastError());
+  return 0;
 }

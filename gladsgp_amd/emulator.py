@@ -151,7 +151,8 @@ class EmulatorData:
         sd_.y_mean, sd_.y_sd = mu, sd
         # rows padded to a multiple of 16 doubles (128 B): every row of the ensemble starts
         # 16-B aligned, so the randomized SVD's ensemble-streaming products read it with 16-B
-        # loads (blas.hip tsk16 / tsm16); y_std is a (n x ny) view of the padded buffer
+        # loads (the 16-B form of blas.hip's gemm_tsk_kernel); y_std is a (n x ny) view of the
+        # padded buffer
         n, ny = sd_.y_dev.shape
         ld = (ny + 15) // 16 * 16
         out = torch.empty((n, ld), dtype=F64, device=sd_.y_dev.device)[:, :ny]

@@ -446,6 +446,114 @@ def test_factorisation_return_codes(lib, table):
         (change, rc, g) for (change, rc), g in zip(rows, got) if g != rc]
 
 
+# gp_dgemm_ws_bytes(m, n, k): the largest workspace any plan for the size takes (blas.hip
+# gemm_plan): split-K slabs of the general kernel (s m n 8 bytes, s the power of two that
+# choose_splits picks) or, at n <= 32 and k >= 65536, the tsk slices (ceil(k / kslice) m n 8,
+# kslice = ceil(k / max(1, 512 / ceil(m / 256))) rounded up to 16).
+_GEMM_WS_BYTES = [
+    ((1, 1, 1), 0), ((70, 33, 129), 0), ((17, 5, 60000), 87040),
+    ((512, 25, 65535), 6553600), ((512, 25, 65536), 26214400), ((512, 25, 70001), 24985600),
+    ((512, 7, 69992), 6995968), ((700, 7, 65537), 6428800), ((512, 33, 70000), 8650752),
+    ((300, 32, 65536), 19660800), ((20001, 25, 300), 0), ((25, 20001, 300), 0),
+    ((512, 25, 1347945), 26214400), ((0, 5, 5), 0)]
+
+
+def test_gemm_workspace_bytes(lib):
+    got = [lib.gp_dgemm_ws_bytes(*mnk) for mnk, _ in _GEMM_WS_BYTES]
+    assert got == [b for _, b in _GEMM_WS_BYTES], [
+        (mnk, b, g) for (mnk, b), g in zip(_GEMM_WS_BYTES, got) if g != b]
+    for mnk in ((5, 0, 5), (5, 5, 0), (-1, 5, 5), (5, 5, -1)):
+        assert lib.gp_dgemm_ws_bytes(*mnk) == 0, mnk
+
+
+# Return codes of the fit-side entry points of blas.hip, in the form of the tables above: the
+# base is a valid no-op (m = 0, ny = 0), so no row reaches a launch; rows with two faults pin
+# the order of the checks.
+_GEMM_ORDER = ["transa", "transb", "m", "n", "k", "alpha", "A", "a_f32", "lda", "B", "b_f32",
+               "ldb", "beta", "C", "ldc", "ws", "ws_bytes", "stream"]
+_GEMM_BASE = dict(transa=0, transb=0, m=0, n=5, k=3, alpha=1.0, A=_P, a_f32=0, lda=1, B=_P,
+                  b_f32=0, ldb=3, beta=0.0, C=_P, ldc=1, ws=None, ws_bytes=0, stream=None)
+_GEMM_M4 = dict(m=4, lda=4, ldc=4)               # m > 0: such a row must fail validation
+
+
+def _rows_gemm(c):
+    """c maps gp_gemm_ex's argument names to the entry point's codes."""
+    return [(dict(transa=2), -1), (dict(transa=-1), -1), (dict(transb=2), -2), (dict(m=-1), -3),
+            (dict(n=-1), -4), (dict(k=-1), -5), (dict(A=None), c["A"]),
+            (dict(A=None, B=None, k=0), 0),                 # k = 0: neither operand is read
+            (dict(lda=0), c["lda"]), (dict(_GEMM_M4, lda=3), c["lda"]),
+            (dict(transa=1, lda=2), c["lda"]),              # op(A) = A^T: lda >= k
+            (dict(transa=1, lda=3), 0),
+            (dict(B=None), c["B"]), (dict(ldb=2), c["ldb"]),
+            (dict(transb=1, ldb=4), c["ldb"]),              # op(B) = B^T: ldb >= n
+            (dict(transb=1, ldb=5), 0),
+            (dict(C=None), c["C"]), (dict(ldc=0), c["ldc"]), (dict(_GEMM_M4, ldc=3), c["ldc"]),
+            (dict(_GEMM_M4, n=0), 0), (dict(n=0, k=0), 0),
+            (dict(transa=2, C=None), -1), (dict(transb=2, m=-1), -2), (dict(m=-1, n=-1), -3),
+            (dict(k=-1, A=None), -5), (dict(A=None, lda=0), c["A"]), (dict(lda=0, B=None), c["lda"]),
+            (dict(B=None, ldb=2), c["B"]), (dict(ldb=2, C=None), c["ldb"]),
+            (dict(C=None, ldc=0), c["C"])]
+
+
+def _gemm_ex_table():
+    c = dict(A=-7, lda=-9, B=-10, ldb=-12, C=-14, ldc=-15)
+    rows = _rows_gemm(c) + [(dict(a_f32=2), -8), (dict(a_f32=-1), -8), (dict(b_f32=2), -11),
+                            (dict(A=None, a_f32=2), -7), (dict(a_f32=2, lda=0), -8),
+                            (dict(B=None, b_f32=2), -10), (dict(b_f32=2, ldb=2), -11),
+                            (dict(a_f32=1, b_f32=1), 0)]
+    return "gp_gemm_ex", _GEMM_ORDER, _GEMM_BASE, rows
+
+
+def _dgemm_table():
+    """gp_dgemm's own argument numbers: A, lda = 7, 8; B, ldb = 9, 10; C, ldc = 12, 13."""
+    c = dict(A=-7, lda=-8, B=-9, ldb=-10, C=-12, ldc=-13)
+    order = [k for k in _GEMM_ORDER if k not in ("a_f32", "b_f32")]
+    return "gp_dgemm", order, {k: _GEMM_BASE[k] for k in order}, _rows_gemm(c)
+
+
+def _sim_stats_table():
+    order = ["Y", "n", "ny", "ldy", "sd_floor", "mu", "sd", "stream"]
+    base = dict(Y=_P, n=3, ny=0, ldy=0, sd_floor=1e-6, mu=_P, sd=_P, stream=None)
+    rows = [(dict(Y=None), -1), (dict(n=0), -2), (dict(n=-1), -2), (dict(ny=-1), -3),
+            (dict(ny=5, ldy=4), -4), (dict(ldy=-1), -4), (dict(mu=None), -6), (dict(sd=None), -7),
+            (dict(n=1), 0), (dict(ldy=7), 0),
+            (dict(Y=None, n=0), -1), (dict(n=0, ny=-1), -2), (dict(ny=-1, ldy=-2), -3),
+            (dict(ldy=-1, mu=None), -4), (dict(mu=None, sd=None), -6)]
+    return "gp_sim_stats", order, base, rows
+
+
+def _standardize_table():
+    order = ["Y", "n", "ny", "ldy", "mu", "sd", "out", "ldo", "inverse", "stream"]
+    base = dict(Y=_P, n=3, ny=0, ldy=0, mu=_P, sd=_P, out=_P, ldo=0, inverse=0, stream=None)
+    rows = [(dict(Y=None), -1), (dict(n=-1), -2), (dict(ny=-1), -3), (dict(ny=5, ldy=4, ldo=5), -4),
+            (dict(ldy=-1), -4), (dict(mu=None), -5), (dict(sd=None), -6), (dict(out=None), -7),
+            (dict(ny=5, ldy=5, ldo=4), -8), (dict(ldo=-1), -8),
+            (dict(n=0, ny=5, ldy=5, ldo=5), 0), (dict(inverse=1), 0),
+            (dict(Y=None, n=-1), -1), (dict(n=-1, ny=-1), -2), (dict(ny=-1, ldy=-2), -3),
+            (dict(ldy=-1, mu=None), -4), (dict(mu=None, sd=None), -5), (dict(sd=None, out=None), -6),
+            (dict(out=None, ldo=-1), -7)]
+    return "gp_standardize", order, base, rows
+
+
+@pytest.mark.parametrize("table", [_gemm_ex_table, _dgemm_table, _sim_stats_table,
+                                   _standardize_table], ids=lambda t: t.__name__.strip("_"))
+def test_fitside_return_codes(lib, table):
+    """gp_gemm_ex, gp_dgemm, gp_sim_stats and gp_standardize: which argument is reported, and
+    in which order, before anything is enqueued."""
+    name, order, base, rows = table()
+    assert sorted(order) == sorted(base), name
+    fn = getattr(lib, name)
+    got = []
+    for change, rc in [({}, 0)] + rows:
+        assert set(change) <= set(base), (name, change)
+        args = dict(base, **change)
+        # a row that passed validation with work to do would launch on the dummy pointers
+        assert rc < 0 or 0 in (args.get("m", 1), args["n"], args.get("ny", 1)), (name, change)
+        got.append(fn(*[args[k] for k in order]))
+    assert got == [0] + [rc for _, rc in rows], [
+        (change, rc, g) for (change, rc), g in zip([({}, 0)] + rows, got) if g != rc]
+
+
 def test_required_alignment_return_codes(lib):
     """The operands whose alignment the header requires (include/gpfit.h, layout contract): a
     16-B aligned L^-1 / packed P with an even ldinv and strideInv, a 256-B aligned workspace.

@@ -57,13 +57,19 @@ def test_gemm(dev, ta, tb, m, n, k):
                                    (512, 25, 70001), (700, 7, 65537), (20001, 25, 300),
                                    (25, 20001, 300), (32, 9000, 512),
                                    # even leading dimensions: the fp64 tsk runs take the
-                                   # 16-B tsk16 form, the float32 runs the 8-B one
+                                   # 16-B tsk form, the float32 runs the 8-B one
                                    (512, 25, 70000), (20000, 25, 300),
                                    # narrow side < 16 (tsm, tsm_t), K = 16, a last tsk slice of
                                    # 8 (69992) or 16 (70000 above) k
                                    (20001, 7, 300), (7, 20001, 300), (20001, 15, 300),
                                    (1, 20001, 300), (16, 20001, 16), (20001, 16, 16),
-                                   (512, 25, 69992), (512, 7, 70000)])
+                                   (512, 25, 69992), (512, 7, 70000),
+                                   # tsk slices of 144 k (9 groups of 16, 18 of 8: the unrolled
+                                   # ring is left mid-way on every slice, in both forms): one
+                                   # full row group with a last slice of 48; 65 rows (waves 2
+                                   # and 3 all masked), N = 32 exactly, a last slice of 17;
+                                   # one row and one column (both column indices clamped)
+                                   (256, 25, 66000), (65, 32, 65537), (1, 1, 65536)])
 def test_gemm_float32_operands_bit_identical(dev, ta, tb, m, n, k):
     """gp_gemm_ex with a float32 A and/or B (widened on load) equals gp_gemm_ex / gp_dgemm on
     fp64 copies of the same values bit for bit, split-K shapes included (512 x 25 x 40000 is
@@ -92,10 +98,13 @@ def test_gemm_float32_operands_bit_identical(dev, ta, tb, m, n, k):
 
 
 @pytest.mark.parametrize("kind", ["tsk", "tsm", "tsm_t"])
-@pytest.mark.parametrize("big,runs", [(70001, None), (20001, None), (20001, 16), (70000, 16)])
+@pytest.mark.parametrize("big,runs", [(70001, None), (20001, None), (20001, 16), (70000, 16),
+                                      # tsk slices of 144 k, all unmasked (one full row group);
+                                      # 65 rows with a pair straddling the odd row end
+                                      (66000, 256), (65537, 65)])
 def test_tall_skinny_padded_ld_matches_unpadded(dev, kind, big, runs):
     """The ensemble's padded row stride (emulator.standardize_y) selects the 16-B tsk form
-    (blas.hip tsk16); every tall-skinny product on the padded ensemble equals the one on an
+    (blas.hip gemm_tsk_kernel, V16); every tall-skinny product on the padded ensemble equals the one on an
     unpadded copy bit for bit, odd lengths (a 16-B pair straddling the row end, zeroed)
     included, and numpy within 1e-12."""
     from gladsgp_amd.blas import CM, gemm

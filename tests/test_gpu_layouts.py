@@ -647,7 +647,7 @@ def _ts_mats(kind):
 @pytest.mark.parametrize("kind", ["tsk", "tsm", "tsm_t"])
 def test_gemm_tall_skinny_big_operand_off8(dev, kind):
     """The big operand of each tall-skinny kernel at an even ld with an 8-B-only base: the 16-B
-    tsk16 form must be refused (blas.hip ts_vec_ok); the result is the tight call's bits."""
+    tsk form must be refused (blas.hip ts_vec_ok); the result is the tight call's bits."""
     ta, tb, m, n, k = _TS[kind]
     A, B, C0 = _cached(("ts_in", kind), lambda: _ts_mats(kind))
     tight = _run_gemm(dev, ta, tb, A, B, C0, ["tight"] * 3, track=False)
