@@ -11,9 +11,29 @@
 #include <type_traits>
 #include <stdint.h>
 
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 #define GP_DEV __device__ __forceinline__
+
+// Two consecutive doubles at an even row: one 16-B load where the layout allows it.
+GP_DEV f64x2 load2(const double* p, int vec) {
+  f64x2 v;
+  if (vec) {
+    v = *reinterpret_cast<const f64x2*>(p);
+  } else {
+    v.x = p[0];
+    v.y = p[1];
+  }
+  return v;
+}
+
+// Sum over the 64 lanes of a wave (xor tree, offsets 32 .. 1): every lane gets the same bits.
+GP_DEV double wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
 
 GP_DEV f64x4 mfma16x16x4(double a, double b, f64x4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -209,6 +229,7 @@ __host__ __device__ inline int gp_ceil_div(long long a, long long b) { return (i
 
 // ---- Host helpers shared by the entry points --------------------------------------------------
 constexpr long long align256(long long bytes) { return ((bytes + 255) / 256) * 256; }
+constexpr int kMaxGridY = 65535;     // grid.y limit: batches beyond it go in several launches
 
 // in an entry point: a HIP error ends the call with its C-ABI code (include/gpfit.h)
 #define GP_CK(x)                                            \

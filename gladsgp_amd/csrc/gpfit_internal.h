@@ -2,19 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// z_b[r] = sum_{k<=r, k<n} Linv_b[r,k] w_b[k] for r0 <= r < r1   (linalg.hip)
-hipError_t gpfit_trmv_rows_launch(const double* Linv, int ld, long long sL, const double* w,
-                                  int ldw, double* z, int ldz, int r0, int r1, int n, int batch,
-                                  hipStream_t st);
-hipError_t gpfit_trmv_launch(const double* Linv, int ld, long long sL, const double* w,
-                             int ldw, double* z, int ldz, int rows, int n, int batch,
+// z_b[r] = sum_{k<=r} Linv_b[r,k] w_b[k] for r < n (linalg.hip).  masked: L[r,k] is taken as zero
+// for k > r whatever the buffer holds there (the same bits as the plain form on a buffer with a
+// zeroed upper triangle).
+hipError_t gpfit_trmv_launch(bool masked, const double* Linv, int ld, long long sL,
+                             const double* w, int ldw, double* z, int ldz, int n, int batch,
                              hipStream_t st);
-
-// gpfit_trmv_launch over all n rows that takes L[r,k] as zero for k > r whatever the buffer holds
-// there (gp_xval: the same bits as gpfit_trmv_launch on a buffer with a zeroed upper triangle).
-hipError_t gpfit_trmv_masked_launch(const double* Linv, int ld, long long sL, const double* w,
-                                    int ldw, double* z, int ldz, int n, int batch,
-                                    hipStream_t st);
 
 constexpr int GPFIT_POTRF_NB = 64;   // column block of gp_potrf_inv (chol.hip NB)
 

@@ -1,5 +1,5 @@
-// gp_alpha / gp_mean_response: mean-response surfaces (main effects and input pairs) of the
-// posterior mean in closed form.  With A = G + delta I, alpha = A^-1 w = L^-T (L^-1 w) and the
+// gp_mean_response: mean-response surfaces (main effects and input pairs) of the posterior mean
+// in closed form.  With A = G + delta I, alpha = A^-1 w (gp_alpha, linalg.hip) and the
 // ARD kernel a product over dimensions, the posterior mean at x_d1 = t1[a1], x_d2 = t2[a2],
 // averaged over I integration points in the other dimensions, is
 //   R[a2, a1] = s sum_n alpha_n M_n exp(-beta_d1 (x_n,d1 - t1[a1])^2) exp(-beta_d2 (x_n,d2 - t2[a2])^2)
@@ -9,10 +9,6 @@
 // integration point) and averages: 8 SepiaEmulatorPrediction calls of 220 points for the main
 // effects, 121 calls of 10 points per pair, each refactorising every (sample, PC) GP.
 //
-//   z            : the triangular gemv of linalg.hip (masked form) into the workspace
-//   alpha        : one wave per column i, sum_{k >= i} L^-1[k,i] z_k, 16-B loads from the
-//                  column's 16-row tile on (xval_loo's alpha term); bound by the 4 n^2 bytes of
-//                  the lower triangle
 //   response     : one 256-thread workgroup per (problem, effect).  Xint, t1, t2 and the
 //                  problem's beta are staged in LDS.  The training rows go by in chunks of 256,
 //                  one row per thread: M_n with one exp per integration point on the summed
@@ -34,12 +30,9 @@
 // fp64 VALU rate.  Measured on one MI355X (HIP events): 4096 GPs x 8 main effects
 // at n = 512, T = 11, I = 20 in 0.96 ms, about a third of the data-sheet fp64 vector rate by the
 // operation count above; 16 GPs x 8 main effects 0.043 ms and x 1 pair of 11 x 11 0.049 ms
-// (launch-bound); gp_alpha 0.32 ms for 512 GPs of n = 512.
+// (launch-bound).
 #include "gpfit_common.h"
-#include "gpfit_internal.h"
 #include "../../include/gpfit.h"
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -52,20 +45,6 @@ constexpr int kRS = kSub + 2;                 // doubles between two panel colum
                                               // operand reads (16 columns x 2 rows per 32 lanes)
                                               // hit 32 different 8-B banks
 constexpr int kIB = 8;                        // integration points per pass over a row
-constexpr int kMaxGridY = 65535;
-
-struct AlphaArgs {
-  const double* Linv;
-  int ld;
-  long long sL;
-  int n;
-  const double* z;        // workspace: z_b = L_b^-1 w_b at z + b * ldz
-  int ldz;
-  double* alpha;
-  int lda;
-  int b0;                 // first problem of this launch (grid.y is limited)
-  int vec;                // L^-1 16-B aligned with even ld / stride: 16-B loads
-};
 
 struct RespArgs {
   const double* X;
@@ -87,48 +66,6 @@ struct RespArgs {
   int b0;
   int eff[2 * kMaxEffects];
 };
-
-GP_DEV f64x2 load2(const double* p, int vec) {
-  f64x2 v;
-  if (vec) {
-    v = *reinterpret_cast<const f64x2*>(p);
-  } else {
-    v.x = p[0];
-    v.y = p[1];
-  }
-  return v;
-}
-
-GP_DEV double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
-// alpha_i = sum_{k >= i} L^-1[k,i] z_k, one wave per column.
-__global__ __launch_bounds__(256) void alpha_kernel(AlphaArgs a) {
-  const int b = a.b0 + blockIdx.y;
-  const int col = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int n = a.n;
-  if (col >= n) return;
-  const double* Lc = a.Linv + b * a.sL + (long long)col * a.ld;
-  const double* zb = a.z + (long long)b * a.ldz;
-  double al0 = 0.0, al1 = 0.0;
-  // rows r, r + 1 with r even: r + 1 <= n - 1, or n is odd and r + 1 = n < gp_padded_n(n)
-  for (int r = (col & ~15) + 2 * lane; r < n; r += 128) {
-    const f64x2 v = load2(Lc + r, a.vec);
-    const f64x2 zz = *reinterpret_cast<const f64x2*>(zb + r);
-    const bool in1 = r + 1 < n;
-    const double x0 = r >= col ? v.x : 0.0;
-    const double x1 = (in1 && r + 1 >= col) ? v.y : 0.0;
-    const double z1 = in1 ? zz.y : 0.0;
-    al0 = fma(x0, zz.x, al0);
-    al1 = fma(x1, z1, al1);
-  }
-  const double al = wave_sum(al0 + al1);
-  if (lane == 0) a.alpha[(long long)b * a.lda + col] = al;
-}
 
 // One (problem, effect): PAIR = false the T1 values of a main effect, true the T2 x T1 surface.
 template <bool PAIR>
@@ -269,58 +206,7 @@ __global__ __launch_bounds__(256) void response_kernel(RespArgs a) {
   }
 }
 
-long long up256(long long b) { return (b + 255) & ~255LL; }
-
 }  // namespace
-
-extern "C" long long gp_alpha_ws_bytes(int n, int batch) {
-  if (n < 0 || batch < 0) return -1;
-  if (n == 0 || batch == 0) return 0;
-  return up256(8LL * batch * gp_padded_n(n));          // z = L^-1 w of every problem
-}
-
-extern "C" int gp_alpha(const double* Linv, int ldinv, long long strideInv, int n,
-                        const double* w, int ldw, double* alpha, int lda, int batch, void* ws,
-                        long long ws_bytes, hipStream_t stream) {
-  if (!Linv) return -1;
-  if (n < 0) return -4;
-  if (batch < 0) return -9;
-  const int npad = gp_padded_n(n);
-  if (ldinv < npad || ldinv < 1) return -2;
-  if (batch > 1 && strideInv < (long long)ldinv * npad) return -3;
-  if (!w) return -5;
-  if (ldw < n && batch > 1) return -6;
-  if (!alpha) return -7;
-  if (lda < n && batch > 1) return -8;
-  if (n == 0 || batch == 0) return 0;
-  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return -10;
-  if (ws_bytes < gp_alpha_ws_bytes(n, batch)) return -11;
-
-  AlphaArgs a;
-  a.Linv = Linv;
-  a.ld = ldinv;
-  a.sL = batch > 1 ? strideInv : 0;
-  a.n = n;
-  a.z = static_cast<const double*>(ws);
-  a.ldz = npad;
-  a.alpha = alpha;
-  a.lda = batch > 1 ? lda : 0;
-  a.vec = !(reinterpret_cast<uintptr_t>(Linv) & 15) && !(ldinv & 1) && !(a.sL & 1);
-  const int ldw_ = batch > 1 ? ldw : 0;
-
-  hipError_t e = hipSuccess;
-  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
-    const int nb = batch - b0 < kMaxGridY ? batch - b0 : kMaxGridY;
-    a.b0 = b0;
-    e = gpfit_trmv_masked_launch(Linv + b0 * a.sL, ldinv, a.sL, w + (long long)b0 * ldw_, ldw_,
-                                 static_cast<double*>(ws) + (long long)b0 * npad, npad, n, nb,
-                                 stream);
-    if (e != hipSuccess) break;
-    hipLaunchKernelGGL(alpha_kernel, dim3(gp_ceil_div(n, 4), nb), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
-}
 
 extern "C" int gp_mean_response_max_grid(void) { return kMaxGrid; }
 extern "C" int gp_mean_response_max_int_elems(void) { return kMaxIntElems; }

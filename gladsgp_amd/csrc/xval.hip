@@ -6,10 +6,11 @@
 // SEPIA's SepiaXvalEmulatorPrediction refits a sub-model per fold (assess_all_models.py:32,
 // include_trunc_error.py:15 import it); here every fold is one pass over its panel.
 //
-//   z            : the triangular gemv of linalg.hip (masked form) into the workspace
+//   z            : the triangular gemv of linalg.hip (masked form) into the workspace, chunked
+//                  and launched by linv_vec.h's driver
 //   xval_loo     : singleton folds, one wave per column: sum L^-1[k,i]^2 and sum L^-1[k,i] z_k
-//                  over k >= i, 16-B loads from the column's 16-row tile on; bound by the
-//                  4 n^2 bytes of the lower triangle
+//                  over k >= i by linv_vec.h's column pass (the one gp_alpha runs), 16-B loads
+//                  from the column's 16-row tile on; bound by the 4 n^2 bytes of the lower triangle
 //   xval_fold    : 2 <= f <= 64, one workgroup per (problem, fold): the panel rows from
 //                  min(F) down are staged 64 at a time in LDS (16-B loads down each gathered
 //                  column), Q_FF accumulates on v_mfma_f64_16x16x4_f64 (the lower 16 x 16 tiles,
@@ -21,11 +22,7 @@
 // not VALU for Q_FF: both have the same fp64 rate on gfx950, but a VALU contraction of the LDS
 // panel needs two LDS operand reads per fma where the MFMA needs one per 16 (not measured
 // against each other).
-#include "gpfit_common.h"
-#include "gpfit_internal.h"
-#include "../../include/gpfit.h"
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
+#include "linv_vec.h"
 
 namespace {
 
@@ -35,17 +32,11 @@ constexpr int kRS = kChunk + 2;       // doubles between two panel columns in LD
                                       // operand reads (16 columns x 2 rows per 32 lanes) hit 32
                                       // different 8-B banks, and every column stays 16-B aligned
 constexpr int kQS = kMaxFold + 1;     // row stride of Q_FF / R / M in LDS
-constexpr int kMaxGridY = 65535;
 
 struct XvalArgs {
-  const double* Linv;
-  int ld;
-  long long sL;
-  int n;
+  LinvVec v;              // L^-1, z and the launch's first problem
   const double* w;
   int ldw;
-  const double* z;        // workspace: z_b = L_b^-1 w_b at z + b * ldz
-  int ldz;
   const int* fold_ptr;
   const int* fold_idx;
   int nfolds, nidx;
@@ -54,8 +45,6 @@ struct XvalArgs {
   double* var;
   int ldo;
   int* info;
-  int b0;                 // first problem of this launch (grid.y is limited)
-  int vec;                // L^-1 16-B aligned with even ld / stride: 16-B loads
 };
 
 // info[b]: -2 (an invalid fold) wins, otherwise the smallest failing fold + 1.
@@ -72,30 +61,12 @@ GP_DEV void report(int* info, int b, int v) {
   }
 }
 
-// Two consecutive doubles at an even row: one 16-B load where the layout allows it.
-GP_DEV f64x2 load2(const double* p, int vec) {
-  f64x2 v;
-  if (vec) {
-    v = *reinterpret_cast<const f64x2*>(p);
-  } else {
-    v.x = p[0];
-    v.y = p[1];
-  }
-  return v;
-}
-
-GP_DEV double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
 // Singleton folds (fold_ptr == NULL: fold i = {i} for every i < n), one wave per fold.
 __global__ __launch_bounds__(256) void xval_loo_kernel(XvalArgs a) {
-  const int b = a.b0 + blockIdx.y;
+  const int b = a.v.b0 + blockIdx.y;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const int n = a.n;
+  const int n = a.v.n;
   int col;
   if (a.fold_ptr) {
     if (j >= a.nfolds) return;
@@ -114,24 +85,8 @@ __global__ __launch_bounds__(256) void xval_loo_kernel(XvalArgs a) {
     if (j >= n) return;
     col = j;
   }
-  const double* Lc = a.Linv + b * a.sL + (long long)col * a.ld;
-  const double* zb = a.z + (long long)b * a.ldz;
-  double q0 = 0.0, q1 = 0.0, al0 = 0.0, al1 = 0.0;
-  // rows r, r + 1 with r even: r + 1 <= n - 1, or n is odd and r + 1 = n < gp_padded_n(n)
-  for (int r = (col & ~15) + 2 * lane; r < n; r += 128) {
-    const f64x2 v = load2(Lc + r, a.vec);
-    const f64x2 zz = *reinterpret_cast<const f64x2*>(zb + r);
-    const bool in1 = r + 1 < n;
-    const double x0 = r >= col ? v.x : 0.0;
-    const double x1 = (in1 && r + 1 >= col) ? v.y : 0.0;
-    const double z1 = in1 ? zz.y : 0.0;
-    q0 = fma(x0, x0, q0);
-    q1 = fma(x1, x1, q1);
-    al0 = fma(x0, zz.x, al0);
-    al1 = fma(x1, z1, al1);
-  }
-  const double q = wave_sum(q0 + q1);
-  const double al = wave_sum(al0 + al1);
+  const LinvColSums cs = linv_col_sums<true>(a.v, b, col, lane);
+  const double q = cs.sq, al = cs.zdot;
   if (lane == 0) {
     const double sh = a.shift ? a.shift[b] : 0.0;
     double m, v;
@@ -153,7 +108,7 @@ template <int T>
 GP_DEV void fold_accumulate(const XvalArgs& a, const double* Lb, const double* zb, const int* idx,
                             int f, int r0, double* panel, double* zs, double* apart) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n = a.n;
+  const int n = a.v.n;
   f64x4 acc[T * (T + 1) / 2];
 #pragma unroll
   for (int p = 0; p < T * (T + 1) / 2; ++p) acc[p] = zero4();
@@ -167,7 +122,7 @@ GP_DEV void fold_accumulate(const XvalArgs& a, const double* Lb, const double* z
       if (c < f && row < n) {
         const int ci = idx[c];
         if (row + 1 >= ci) {
-          v = load2(Lb + (long long)ci * a.ld + row, a.vec);
+          v = load2(Lb + (long long)ci * a.v.ld + row, a.v.vec);
           if (row < ci) v.x = 0.0;
           if (row + 1 >= n) v.y = 0.0;
         }
@@ -226,9 +181,9 @@ __global__ __launch_bounds__(256) void xval_fold_kernel(XvalArgs a) {
   __shared__ int idx[kMaxFold];
   __shared__ int meta[2];
   static_assert(kMaxFold * kQS <= kMaxFold * kRS, "Q_FF aliases the panel");
-  const int fold = blockIdx.x, b = a.b0 + blockIdx.y;
+  const int fold = blockIdx.x, b = a.v.b0 + blockIdx.y;
   const int tid = threadIdx.x;
-  const int n = a.n;
+  const int n = a.v.n;
   const int p0 = a.fold_ptr[fold], p1 = a.fold_ptr[fold + 1];
   const int f = p1 - p0;
   if (f == 0 || f == 1) return;                // empty, or xval_loo_kernel's
@@ -253,8 +208,8 @@ __global__ __launch_bounds__(256) void xval_fold_kernel(XvalArgs a) {
     return;
   }
   const int r0 = meta[1] & ~15;
-  const double* Lb = a.Linv + b * a.sL;
-  const double* zb = a.z + (long long)b * a.ldz;
+  const double* Lb = a.v.Linv + b * a.v.sL;
+  const double* zb = a.v.z + (long long)b * a.v.ldz;
   switch ((f + 15) >> 4) {
     case 1: fold_accumulate<1>(a, Lb, zb, idx, f, r0, panel, zs, apart); break;
     case 2: fold_accumulate<2>(a, Lb, zb, idx, f, r0, panel, zs, apart); break;
@@ -312,8 +267,6 @@ __global__ __launch_bounds__(256) void xval_fold_kernel(XvalArgs a) {
   if (!ok && i == 0) report(a.info, b, fold + 1);
 }
 
-long long up256(long long b) { return (b + 255) & ~255LL; }
-
 }  // namespace
 
 extern "C" int gp_xval_max_fold(void) { return kMaxFold; }
@@ -321,7 +274,7 @@ extern "C" int gp_xval_max_fold(void) { return kMaxFold; }
 extern "C" long long gp_xval_ws_bytes(int n, int nfolds, int nidx, int batch) {
   if (n < 0 || nfolds < 0 || nidx < 0 || batch < 0) return -1;
   if (n == 0 || batch == 0) return 0;
-  return up256(8LL * batch * gp_padded_n(n));          // z = L^-1 w of every problem
+  return linv_vec_ws_bytes(n, batch);
 }
 
 extern "C" int gp_xval(const double* Linv, int ldinv, long long strideInv, int n,
@@ -352,14 +305,9 @@ extern "C" int gp_xval(const double* Linv, int ldinv, long long strideInv, int n
   if (fold_ptr && nfolds == 0) return 0;
 
   XvalArgs a;
-  a.Linv = Linv;
-  a.ld = ldinv;
-  a.sL = batch > 1 ? strideInv : 0;
-  a.n = n;
+  a.v = linv_vec_operands(Linv, ldinv, strideInv, n, batch, ws);
   a.w = w_hat;
   a.ldw = batch > 1 ? ldw : 0;
-  a.z = static_cast<const double*>(ws);
-  a.ldz = npad;
   a.fold_ptr = fold_ptr;
   a.fold_idx = fold_idx;
   a.nfolds = nfolds;
@@ -369,23 +317,17 @@ extern "C" int gp_xval(const double* Linv, int ldinv, long long strideInv, int n
   a.var = var;
   a.ldo = batch > 1 ? ldo : 0;
   a.info = info;
-  a.vec = !(reinterpret_cast<uintptr_t>(Linv) & 15) && !(ldinv & 1) && !(a.sL & 1);
 
   hipError_t e = hipSuccess;
   if (info) e = hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, stream);
-  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
-    const int nb = batch - b0 < kMaxGridY ? batch - b0 : kMaxGridY;
-    a.b0 = b0;
-    e = gpfit_trmv_masked_launch(Linv + b0 * a.sL, ldinv, a.sL, w_hat + (long long)b0 * a.ldw,
-                                 a.ldw, static_cast<double*>(ws) + (long long)b0 * npad, npad, n,
-                                 nb, stream);
-    if (e != hipSuccess) break;
-    const int jobs = fold_ptr ? nfolds : n;
-    hipLaunchKernelGGL(xval_loo_kernel, dim3(gp_ceil_div(jobs, 4), nb), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess || !fold_ptr) continue;
-    hipLaunchKernelGGL(xval_fold_kernel, dim3(nfolds, nb), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess)
+    e = linv_vec_run(a.v, w_hat, ldw, batch, stream, [&](int nb) {
+      const int jobs = fold_ptr ? nfolds : n;
+      hipLaunchKernelGGL(xval_loo_kernel, dim3(gp_ceil_div(jobs, 4), nb), dim3(256), 0, stream, a);
+      const hipError_t el = hipGetLastError();
+      if (el != hipSuccess || !fold_ptr) return el;
+      hipLaunchKernelGGL(xval_fold_kernel, dim3(nfolds, nb), dim3(256), 0, stream, a);
+      return hipGetLastError();
+    });
   return e == hipSuccess ? 0 : GPFIT_ERR_HIP - (int)e;
 }

@@ -148,12 +148,13 @@ class Workspace:
         return self.buf
 
 
-_POTRF_WS = {}
+_SCRATCH = {}
 
 
-def _potrf_ws(device, nbytes: int) -> torch.Tensor:
-    w = _POTRF_WS.setdefault(str(device), Workspace())
-    return w.get(nbytes, device)
+def _scratch(name: str, device, nbytes: int) -> torch.Tensor:
+    """The per-device scratch of the entry point family ``name``, reused across calls on the
+    current stream."""
+    return _SCRATCH.setdefault((name, str(device)), Workspace()).get(nbytes, device)
 
 
 def cholesky_inverse(G: torch.Tensor, overwrite: bool = True,
@@ -176,7 +177,7 @@ def cholesky_inverse(G: torch.Tensor, overwrite: bool = True,
     logdet = torch.empty(batch, dtype=F64, device=G.device)
     nbytes = int(_capi.lib().gp_potrf_inv_ws_bytes(n, batch))
     ws = (workspace.get(nbytes, G.device) if workspace is not None
-          else _potrf_ws(G.device, nbytes))
+          else _scratch("potrf", G.device, nbytes))
     _capi.call("gp_potrf_inv_ws", A.data_ptr(), n, n, n * n, Linv.data_ptr(), npad, npad * npad,
                batch, info.data_ptr(), logdet.data_ptr(), ws.data_ptr(), ws.numel(),
                _stream(G.device))
@@ -220,9 +221,6 @@ def pack_linv(chol: Cholesky, out: torch.Tensor | None = None) -> torch.Tensor:
     return out
 
 
-_Z_WS = {}
-
-
 def predict_z(chol, w, out: torch.Tensor | None = None) -> torch.Tensor:
     """z = L^-1 w per problem, (batch, padded_n(n)), zero past n, with exactly the arithmetic
     :func:`predict` applies internally (gp_predict_z); ``chol`` a Cholesky or a PackedLinv."""
@@ -234,7 +232,7 @@ def predict_z(chol, w, out: torch.Tensor | None = None) -> torch.Tensor:
     if out is None:
         out = torch.empty((batch, npad), dtype=F64, device=dev)
     nbytes = int(_capi.lib().gp_predict_z_ws_bytes(n, batch))
-    ws = _Z_WS.setdefault(str(dev), Workspace()).get(nbytes, dev)
+    ws = _scratch("z", dev, nbytes)
     _capi.call("gp_predict_z", L.data_ptr(), npad, L.stride(0),
                _capi.LINV_PACKED if packed else _capi.LINV_PADDED, n, w_t.data_ptr(), n,
                out.data_ptr(), out.stride(0) if batch > 1 else npad, batch, ws.data_ptr(),
@@ -419,19 +417,9 @@ def check_xval_info(info: torch.Tensor) -> None:
         f"Q_FF not positive definite (info = fold + 1 = {vals[bad].tolist()} for problems {bad})")
 
 
-_XVAL_WS = {}
-
-
-def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True):
-    """Cross-validated mean / variance of the training simulations from L^-1, no refit (gp_xval):
-    for every fold F, E[w_F | w outside F] and diag Cov - shift.  Returns (mean, var), each
-    (batch, n); entries whose index is in no fold are NaN (left as they are in ``out``).
-
-    ``folds``: a sequence of index sequences (each at most :func:`xval_max_fold` long, no index
-    twice), or None for leave-one-out; ``shift`` (batch,) or None for 0 (``s + delta - s_pred``
-    gives the variance :func:`predict` reports at a new point placed there); ``w`` a contiguous
-    float64 (batch, n) device tensor.  Everything is validated on the host before the call;
-    ``check`` synchronises and raises like :meth:`Cholesky.check`."""
+def _chol_w(chol, w):
+    """Validate the (chol, w) pair of :func:`xval` / :func:`alpha` short of the device checks,
+    which come after the caller's own: returns (L, dev, batch, n, npad, w), ``w`` as (batch, n)."""
     if not isinstance(chol, Cholesky):
         raise ValueError("chol: expected a kernels.Cholesky (padded L^-1)")
     L = chol.linv_buf
@@ -445,6 +433,22 @@ def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True
         raise ValueError(f"w: expected shape ({batch}, {n}), got {tuple(w.shape)}")
     if not w.is_contiguous():
         raise ValueError("w: expected a contiguous tensor")
+    if L.dtype != F64 or tuple(L.shape) != (batch, npad, npad) or not L.is_contiguous():
+        raise ValueError(f"chol: expected a contiguous float64 ({batch}, {npad}, {npad}) L^-1")
+    return L, dev, batch, n, npad, w
+
+
+def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True):
+    """Cross-validated mean / variance of the training simulations from L^-1, no refit (gp_xval):
+    for every fold F, E[w_F | w outside F] and diag Cov - shift.  Returns (mean, var), each
+    (batch, n); entries whose index is in no fold are NaN (left as they are in ``out``).
+
+    ``folds``: a sequence of index sequences (each at most :func:`xval_max_fold` long, no index
+    twice), or None for leave-one-out; ``shift`` (batch,) or None for 0 (``s + delta - s_pred``
+    gives the variance :func:`predict` reports at a new point placed there); ``w`` a contiguous
+    float64 (batch, n) device tensor.  Everything is validated on the host before the call;
+    ``check`` synchronises and raises like :meth:`Cholesky.check`."""
+    L, dev, batch, n, npad, w = _chol_w(chol, w)
     ptr, idx = _xval_folds(folds, n)
     if shift is not None:
         if not torch.is_tensor(shift) or shift.dtype != F64 or shift.numel() != batch or \
@@ -457,8 +461,6 @@ def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True
                 (batch > 1 and out[0].stride(0) != out[1].stride(0)):
             raise ValueError(f"out: expected two float64 ({batch}, {n}) tensors with unit "
                              "column stride and one row stride")
-    if L.dtype != F64 or tuple(L.shape) != (batch, npad, npad) or not L.is_contiguous():
-        raise ValueError(f"chol: expected a contiguous float64 ({batch}, {npad}, {npad}) L^-1")
     for t, nm in ((L, "chol"), (w, "w")) + (((shift, "shift"),) if shift is not None else ()) + \
             (tuple((t, "out") for t in out) if out is not None else ()):
         _check_device(t, nm)
@@ -478,7 +480,7 @@ def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True
             idx_t[:nidx] = torch.as_tensor(idx, device=dev)
     info = torch.empty(batch, dtype=torch.int32, device=dev)
     nbytes = int(_capi.lib().gp_xval_ws_bytes(n, nfolds, nidx, batch))
-    ws = _XVAL_WS.setdefault(str(dev), Workspace()).get(nbytes, dev)
+    ws = _scratch("xval", dev, nbytes)
     _capi.call("gp_xval", L.data_ptr(), npad, npad * npad, n, w.data_ptr(), n,
                ptr_t.data_ptr() if ptr_t is not None else None,
                idx_t.data_ptr() if idx_t is not None else None, nfolds, nidx,
@@ -490,7 +492,6 @@ def xval(chol: Cholesky, w, folds=None, shift=None, out=None, check: bool = True
     return mean, var
 
 
-_ALPHA_WS = {}
 RESP_ORDER = {"cyclic": 0, "ascending": 1}     # GPFIT_RESP_CYCLIC / GPFIT_RESP_ASCENDING
 RESP_MAX_EFFECTS = 64                          # GPFIT_RESP_MAX_EFFECTS
 
@@ -499,26 +500,12 @@ def alpha(chol: Cholesky, w, out: torch.Tensor | None = None) -> torch.Tensor:
     """alpha = A^-1 w = L^-T (L^-1 w) per problem -> (batch, n) (gp_alpha): the weights of the
     posterior mean, which :func:`mean_response` contracts.  ``w`` a contiguous float64
     (batch, n) device tensor; ``out`` a float64 (batch, n) tensor with unit column stride."""
-    if not isinstance(chol, Cholesky):
-        raise ValueError("chol: expected a kernels.Cholesky (padded L^-1)")
-    L = chol.linv_buf
-    dev, batch, n = L.device, L.shape[0], chol.n
-    npad = padded_n(n)
-    if not torch.is_tensor(w) or w.dtype != F64:
-        raise ValueError("w: expected a float64 tensor")
-    if w.dim() == 1:
-        w = w.reshape(1, -1)
-    if tuple(w.shape) != (batch, n):
-        raise ValueError(f"w: expected shape ({batch}, {n}), got {tuple(w.shape)}")
-    if not w.is_contiguous():
-        raise ValueError("w: expected a contiguous tensor")
+    L, dev, batch, n, npad, w = _chol_w(chol, w)
     if out is not None:
         if not torch.is_tensor(out) or out.dtype != F64 or tuple(out.shape) != (batch, n) or \
                 (n > 1 and out.stride(1) != 1) or (batch > 1 and out.stride(0) < n):
             raise ValueError(f"out: expected a float64 ({batch}, {n}) tensor with unit column "
                              "stride")
-    if L.dtype != F64 or tuple(L.shape) != (batch, npad, npad) or not L.is_contiguous():
-        raise ValueError(f"chol: expected a contiguous float64 ({batch}, {npad}, {npad}) L^-1")
     for t, nm in ((L, "chol"), (w, "w")) + (((out, "out"),) if out is not None else ()):
         _check_device(t, nm)
     if out is None:
@@ -526,7 +513,7 @@ def alpha(chol: Cholesky, w, out: torch.Tensor | None = None) -> torch.Tensor:
     if n == 0 or batch == 0:
         return out
     nbytes = int(_capi.lib().gp_alpha_ws_bytes(n, batch))
-    ws = _ALPHA_WS.setdefault(str(dev), Workspace()).get(nbytes, dev)
+    ws = _scratch("alpha", dev, nbytes)
     _capi.call("gp_alpha", L.data_ptr(), npad, npad * npad, n, w.data_ptr(), n, out.data_ptr(),
                out.stride(0) if batch > 1 else n, batch, ws.data_ptr(), ws.numel(), _stream(dev))
     return out
@@ -805,7 +792,7 @@ def cholesky(G: torch.Tensor, overwrite: bool = True):
     info = torch.empty(batch, dtype=torch.int32, device=G.device)
     logdet = torch.empty(batch, dtype=F64, device=G.device)
     nbytes = int(_capi.lib().gp_potrf_ws_bytes(n, batch))
-    ws = _potrf_ws(G.device, nbytes)
+    ws = _scratch("potrf", G.device, nbytes)
     _capi.call("gp_potrf_ws", A.data_ptr(), n, n, n * n, batch, info.data_ptr(),
                logdet.data_ptr(), ws.data_ptr(), ws.numel(), _stream(G.device))
     return torch.tril(A.transpose(-1, -2)), info, logdet
@@ -963,7 +950,7 @@ def cholesky_inplace(A: torch.Tensor):
     info = torch.zeros(batch, dtype=torch.int32, device=A.device)
     logdet = torch.empty(batch, dtype=F64, device=A.device)
     nbytes = int(_capi.lib().gp_potrf_ws_bytes(n, batch))
-    ws = _potrf_ws(A.device, nbytes)
+    ws = _scratch("potrf", A.device, nbytes)
     _capi.call("gp_potrf_ws", A.data_ptr(), n, n, n * n, batch, info.data_ptr(),
                logdet.data_ptr(), ws.data_ptr(), ws.numel(), _stream(A.device))
     return info, logdet

@@ -97,6 +97,25 @@ def test_null_form_equals_singleton_folds(dev):
     _bits(a[1], b[1])
 
 
+@pytest.mark.parametrize("n", [1, 17, 129, 513])
+def test_leave_one_out_residual_is_alpha_times_var(dev, n):
+    """gp_xval's leave-one-out form and gp_alpha walk the columns of L^-1 with one routine: with
+    al_i = sum_k L^-1[k,i] z_k and q_i = sum_k L^-1[k,i]^2, mean = fl(w - fl(al / q)),
+    var = fl(1 / q) (no shift) and alpha = al with the same bits, so with u = 2^-53
+    |fl(w - mean) - fl(alpha var)| <= u (|mean| + |w - mean|) + 4 u |al / q|.  One row, a partial
+    16-row tile, an odd n across the 128-row stride, several strides; three problems."""
+    from gladsgp_amd import kernels
+    _, ch, w, _ = _factor(dev, n, _d(n), 3)
+    mean, var = kernels.xval(ch, w, None, None)
+    al = kernels.alpha(ch, w)
+    w, mean, var, al = (t.cpu().numpy() for t in (w, mean, var, al))
+    err = np.abs((w - mean) - al * var)
+    bound = 2.0 ** -52 * (np.abs(mean) + 8 * np.abs(al * var))
+    print(f"n={n} max err {err.max():.3e} min slack {(bound - err).min():.3e}")
+    assert np.isfinite(mean).all() and np.isfinite(var).all() and np.isfinite(al).all()
+    assert (err <= bound).all(), np.argwhere(err > bound)[:8]
+
+
 def test_upper_triangle_is_never_read(dev):
     """An L^-1 whose strict upper triangle holds 1e300 gives the bits of the zeroed one, for
     leave-one-out and for folds."""
