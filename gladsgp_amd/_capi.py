@@ -147,6 +147,10 @@ SIGNATURES = {
     "gp_alpha_ws_bytes": (c_ll, [c_int, c_int]),
     "gp_alpha": (c_int, [c_void_p, c_int, c_ll, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                          c_void_p, c_ll, c_void_p]),
+    "gp_nll_grad_ws_bytes": (c_ll, [c_int, c_int, c_int]),
+    "gp_nll_grad": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                            c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_ll,
+                            c_void_p]),
     "gp_mean_response_max_grid": (c_int, []),
     "gp_mean_response_max_int_elems": (c_int, []),
     "gp_mean_response": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,

@@ -335,6 +335,38 @@ class EmulatorModel:
         w = self.w_hat.transpose(0, 1).contiguous()           # (P, n)
         return -float(kernels.nll(ch, w).sum().item())
 
+    def log_likelihood_grad(self, params=None) -> dict:
+        """Gradient of :meth:`log_likelihood` (the log-likelihood summed over PCs, no priors) in
+        the SEPIA parameters: a dict with the keys and shapes of ``params.values()`` -- betaU
+        (d + 1, P) with 0 in the dummy-x row, lamUz and lamWs (1, P), lamWOs (1, 1).
+
+        One batched kernels.nll_value_grad over the P GPs gives dNLL_j / d(s_j, delta_j, beta_jk);
+        the chain rule through :func:`gp_params` (s = 1 / lamUz, delta_j = 1 / lamWs_j +
+        1 / (lamWOs LamSim_j)) and the sign of the log-likelihood give
+        d/dbetaU[1 + k, j] = -dNLL_j/dbeta_k, d/dlamUz_j = dNLL_j/ds / lamUz_j^2,
+        d/dlamWs_j = dNLL_j/ddelta / lamWs_j^2 and d/dlamWOs = sum_j dNLL_j/ddelta /
+        (lamWOs^2 LamSim_j).  Raises like :meth:`log_likelihood` where a Gram is not positive
+        definite."""
+        pr = self.params.values() if params is None else params
+        samples = {k: np.asarray(pr[k]).reshape(1, -1) for k in self.param_names}
+        lam = _np(self.LamSim).reshape(-1)
+        beta, s, delta, _ = gp_params(samples, lam, self.d, self.P, False)
+        dev = self.device
+        w = self.w_hat.transpose(0, 1).contiguous()           # (P, n)
+        _, g, info = kernels.nll_value_grad(
+            self.data.sim_data.t_dev, torch.as_tensor(beta[0], device=dev).contiguous(),
+            torch.as_tensor(s[0], device=dev).contiguous(),
+            torch.as_tensor(delta[0], device=dev).contiguous(), w)
+        kernels.check_info(info)
+        g = g.cpu().numpy()                                   # (P, d + 2)
+        lamUz, lamWs = samples["lamUz"].reshape(-1), samples["lamWs"].reshape(-1)
+        lamWOs = float(samples["lamWOs"].reshape(-1)[0])
+        betaU = np.zeros((self.d + 1, self.P))
+        betaU[1:] = -g[:, 2:].T
+        return {"betaU": betaU, "lamUz": (g[:, 0] / lamUz ** 2).reshape(1, -1),
+                "lamWs": (g[:, 1] / lamWs ** 2).reshape(1, -1),
+                "lamWOs": np.sum(g[:, 1] / (lamWOs ** 2 * lam)).reshape(1, 1)}
+
 
 def fit_ensemble(models, n_burn, n_levels, nsamp, tune=True):
     """Tune and sample a list of EmulatorModels on one design together: the drop-in for the

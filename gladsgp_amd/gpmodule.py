@@ -21,6 +21,10 @@ Every objective evaluation runs on the GPU: Gram (gp_gram_ardse) -> Cholesky + L
 mean and sqrt(marginal variance) at the fitted theta (cell 9's formulas, diagonal only; the
 prior variance at a prediction point is theta0^2 — whether GPmodule adds the nugget there is not
 recorded anywhere in the reference: parity for ``error`` is unpinned at the 1e-6 level).
+
+Beyond the reference: ``fit(..., jac=True)`` gives scipy the analytic gradient (gp_nll_grad, one
+factorisation per value-and-gradient evaluation) instead of letting it difference the objective,
+and ``GP(..., ard=True)`` fits one length scale per input column, theta = [theta0, l_1 .. l_d].
 """
 from __future__ import annotations
 
@@ -39,18 +43,31 @@ def _theta_to_kernel(theta, nugget):
     return theta[0] ** 2, 1.0 / (2.0 * theta[1] ** 2), nugget ** 2
 
 
+def _kernel_params(theta, nugget, d, ard=False):
+    """(s, beta (d,), delta): one length scale for every column, or with ``ard`` theta =
+    [theta0, l_1 .. l_d] and beta_k = 1 / (2 l_k^2)."""
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    if not ard:
+        s, beta, delta = _theta_to_kernel(theta, nugget)
+        return s, np.full(d, beta), delta
+    if theta.size != d + 1:
+        raise ValueError(f"theta: ard=True takes [theta0, l_1 .. l_{d}], got {theta.size} values")
+    return theta[0] ** 2, 1.0 / (2.0 * theta[1:] ** 2), nugget ** 2
+
+
 def squared_exponential(x1, x2, theta, nugget: float = 0.0, device=None):
     """theta0^2 exp(-|x1_i - x2_j|^2 / (2 theta1^2)) (+ nugget^2 on the diagonal when x1 is x2)
-    as a numpy (n1, n2) matrix, built by the gp_cross_ardse kernel."""
+    as a numpy (n1, n2) matrix, built by the gp_cross_ardse kernel.  A theta of more than two
+    values is [theta0, l_1 .. l_d], one length scale per column (GP(ard=True))."""
     dev = _device(device)
     a = np.asarray(x1, dtype=np.float64)
     b = np.asarray(x2, dtype=np.float64)
     a = a.reshape(a.shape[0], -1)
     b = b.reshape(b.shape[0], -1)
-    s, beta, delta = _theta_to_kernel(theta, nugget)
     d = a.shape[1]
+    s, beta, delta = _kernel_params(theta, nugget, d, np.size(theta) > 2)
     Kt = kernels.cross(torch.as_tensor(b, device=dev), torch.as_tensor(a, device=dev),
-                       torch.full((1, d), beta, dtype=F64, device=dev), s)   # (1, n1, n2)
+                       torch.as_tensor(beta, device=dev).reshape(1, d), s)   # (1, n1, n2)
     K = Kt[0].cpu().numpy()
     if x1 is x2 and delta:
         K[np.diag_indices_from(K)] += delta
@@ -68,13 +85,15 @@ def _device(device):
 class GP:
     """GPmodule.GP mirror (fit by maximum likelihood, predict at new points)."""
 
-    def __init__(self, covariance=squared_exponential, cov_para=None, device=None):
+    def __init__(self, covariance=squared_exponential, cov_para=None, device=None,
+                 ard: bool = False):
         if covariance is not squared_exponential:
             raise NotImplementedError("only the squared-exponential covariance is on the GPU path")
         self.covariance_fn = covariance
         self.cov_para = dict(cov_para or {})
         self.nugget = float(self.cov_para.get("nugget", 0.0))
         self.device = _device(device)
+        self.ard = bool(ard)        # theta = [theta0, l_1 .. l_d], one length scale per column
         self.theta = None
         self.minimize_res = None
         self.nfev_gpu = 0
@@ -84,11 +103,15 @@ class GP:
         return squared_exponential(x1, x2, theta, self.nugget if x1 is x2 else 0.0,
                                    self.device)
 
-    def _factor(self, theta):
-        s, beta, delta = _theta_to_kernel(theta, self.nugget)
+    def _params(self, theta):
+        """(s, beta as a (1, d) device tensor, delta) at theta."""
         d = self._X.shape[1]
-        G = kernels.gram(self._X, torch.full((1, d), beta, dtype=F64, device=self.device), s,
-                         delta)
+        s, beta, delta = _kernel_params(theta, self.nugget, d, self.ard)
+        return s, torch.as_tensor(beta, device=self.device).reshape(1, d), delta
+
+    def _factor(self, theta):
+        s, beta, delta = self._params(theta)
+        G = kernels.gram(self._X, beta, s, delta)
         return kernels.cholesky_inverse(G), s, beta
 
     def negloglik(self, theta) -> float:
@@ -100,17 +123,46 @@ class GP:
             return np.inf
         return float(v[0])
 
+    def negloglik_grad(self, theta):
+        """(f, g): the objective of :meth:`negloglik` and its gradient in theta, from one
+        factorisation (kernels.nll_value_grad: the analytic gradient in s, delta, beta on the
+        GPU) and the chain rule through s = theta0^2 and beta_k = 1 / (2 l_k^2):
+        g_0 = 2 theta0 dNLL/ds, g_1 = -theta1^-3 sum_k dNLL/dbeta_k (``ard``: g_{1+k} =
+        -l_k^-3 dNLL/dbeta_k).  (inf, zeros) where K is not positive definite."""
+        theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+        s, beta, delta = self._params(theta)
+        one = lambda v: torch.full((1,), float(v), dtype=F64, device=self.device)  # noqa: E731
+        val, grad, info = kernels.nll_value_grad(self._X, beta, one(s), one(delta), self._y)
+        self.nfev_gpu += 1
+        out = torch.cat([val, grad[0], info.to(F64)]).cpu().numpy()    # the one host sync
+        if out[-1] != 0:
+            return np.inf, np.zeros(theta.size)
+        gb = out[3:-1]
+        gl = -gb / theta[1:] ** 3 if self.ard else np.array([-np.sum(gb) / theta[1] ** 3])
+        return float(out[0]), np.concatenate([[2.0 * theta[0] * out[1]], gl])
+
     # ---------------------------------------------------------------------------- surface
-    def fit(self, x, y, x0, method: str = "BFGS", **minimize_kw):
-        """Maximum-likelihood theta from start x0 (scipy BFGS over the GPU objective).
-        Returns the fitted theta; the scipy result is ``self.minimize_res``."""
+    def set_data(self, x, y):
+        """The training data :meth:`negloglik` and :meth:`negloglik_grad` evaluate on
+        (:meth:`fit` sets it itself)."""
         x = np.asarray(x, dtype=np.float64)
         self._x = x.reshape(x.shape[0], -1)
         self._X = torch.as_tensor(self._x, device=self.device).contiguous()
         self._y_np = np.asarray(y, dtype=np.float64).reshape(-1)
         self._y = torch.as_tensor(self._y_np, device=self.device).reshape(1, -1)
-        res = sopt.minimize(self.negloglik, np.asarray(x0, dtype=np.float64), method=method,
-                            **minimize_kw)
+
+    def fit(self, x, y, x0, method: str = "BFGS", jac: bool = False, **minimize_kw):
+        """Maximum-likelihood theta from start x0 (scipy BFGS over the GPU objective).
+        Returns the fitted theta; the scipy result is ``self.minimize_res``.  ``jac=True`` hands
+        scipy :meth:`negloglik_grad` (value and analytic gradient per evaluation) instead of
+        letting it difference the bare objective."""
+        self.set_data(x, y)
+        if jac:
+            res = sopt.minimize(self.negloglik_grad, np.asarray(x0, dtype=np.float64),
+                                method=method, jac=True, **minimize_kw)
+        else:
+            res = sopt.minimize(self.negloglik, np.asarray(x0, dtype=np.float64), method=method,
+                                **minimize_kw)
         self.minimize_res = res
         self.theta = np.asarray(res.x, dtype=np.float64)
         ch, s, beta = self._factor(self.theta)
@@ -132,11 +184,9 @@ class GP:
     def _predict(self, xpred):
         xp = np.asarray(xpred, dtype=np.float64)
         xp = xp.reshape(xp.shape[0], -1)
-        d = self._x.shape[1]
-        beta = torch.full((1, d), self._beta, dtype=F64, device=self.device)
         mean, var = kernels.predict(self._chol, self._X,
-                                    torch.as_tensor(xp, device=self.device), beta, self._s,
-                                    self._s, self._y)
+                                    torch.as_tensor(xp, device=self.device), self._beta,
+                                    self._s, self._s, self._y)
         return mean[0].cpu().numpy(), var[0].cpu().numpy()
 
     def predictor(self, xpred) -> np.ndarray:

@@ -519,6 +519,67 @@ def alpha(chol: Cholesky, w, out: torch.Tensor | None = None) -> torch.Tensor:
     return out
 
 
+_alpha = alpha            # nll_grad's keyword of the same name hides the function
+
+
+def nll_grad(chol: Cholesky, X, beta, s, w, alpha: torch.Tensor | None = None) -> torch.Tensor:
+    """Gradient of :func:`nll` in the kernel's parameters per problem -> (batch, d + 2), in the
+    order [d/ds, d/ddelta, d/dbeta_0 .. d/dbeta_{d-1}] (gp_nll_grad), from the L^-1 of
+    :func:`cholesky_inverse` with the same X, beta, s.
+
+    ``X`` (n, d), ``beta`` (batch, d), ``s`` (batch,), ``w`` (batch, n): contiguous float64
+    device tensors; ``alpha`` (batch, n) from :func:`alpha`, computed here when not given.  A
+    problem whose factorisation reported info != 0 has an unspecified gradient."""
+    L, dev, batch, n, npad, w = _chol_w(chol, w)
+    _f64_tensor(X, "X", f"({n}, d) with 1 <= d", lambda t: t.dim() == 2 and t.shape[0] == n and
+                t.shape[1] >= 1)
+    d = X.shape[1]
+    _f64_tensor(beta, "beta", f"({batch}, {d})", lambda t: tuple(t.shape) == (batch, d))
+    _f64_tensor(s, "s", f"({batch},)", lambda t: tuple(t.shape) == (batch,))
+    if alpha is not None:
+        _f64_tensor(alpha, "alpha", f"({batch}, {n})", lambda t: tuple(t.shape) == (batch, n))
+    for t, nm in ((L, "chol"), (w, "w"), (X, "X"), (beta, "beta"), (s, "s")) + \
+            (((alpha, "alpha"),) if alpha is not None else ()):
+        _check_device(t, nm)
+    out = torch.empty((batch, d + 2), dtype=F64, device=dev)
+    if n == 0 or batch == 0:
+        return out.zero_()
+    if alpha is None:
+        alpha = _alpha(chol, w)
+    nbytes = int(_capi.lib().gp_nll_grad_ws_bytes(n, d, batch))
+    ws = _scratch("nll_grad", dev, nbytes)
+    _capi.call("gp_nll_grad", L.data_ptr(), npad, npad * npad, X.data_ptr(), d, n, d,
+               beta.data_ptr(), d, s.data_ptr(), alpha.data_ptr(), n, out.data_ptr(), d + 2,
+               batch, ws.data_ptr(), ws.numel(), _stream(dev))
+    return out
+
+
+def nll_value_grad(X, beta, s, delta, w):
+    """Value and gradient of the likelihood of ``batch`` GPs on one design -> (nll, grad, info):
+    Gram -> :func:`cholesky_inverse` -> :func:`nll` -> :func:`alpha` -> :func:`nll_grad`, with
+    no host synchronisation.  ``nll`` (batch,), ``grad`` (batch, d + 2) as :func:`nll_grad`,
+    ``info`` (batch,) int32 the factorisation's; a problem with info != 0 (K not positive
+    definite) has NaN in ``nll`` and in its row of ``grad``, set on the device.
+
+    ``X`` (n, d), ``beta`` (batch, d), ``s``, ``delta`` (batch,), ``w`` (batch, n): contiguous
+    float64 device tensors."""
+    _f64_tensor(X, "X", "(n, d) with 1 <= d", lambda t: t.dim() == 2 and t.shape[1] >= 1)
+    n, d = X.shape
+    _f64_tensor(beta, "beta", f"(batch, {d})", lambda t: t.dim() == 2 and t.shape[1] == d)
+    batch = beta.shape[0]
+    _f64_tensor(s, "s", f"({batch},)", lambda t: tuple(t.shape) == (batch,))
+    _f64_tensor(delta, "delta", f"({batch},)", lambda t: tuple(t.shape) == (batch,))
+    _f64_tensor(w, "w", f"({batch}, {n})", lambda t: tuple(t.shape) == (batch, n))
+    for t, nm in ((X, "X"), (beta, "beta"), (s, "s"), (delta, "delta"), (w, "w")):
+        _check_device(t, nm)
+    ch = cholesky_inverse(gram(X, beta, s, delta, batch=batch))
+    val = nll(ch, w)
+    grad = nll_grad(ch, X, beta, s, w, alpha(ch, w))
+    bad = ch.info != 0
+    nan = torch.full((), float("nan"), dtype=F64, device=X.device)
+    return torch.where(bad, nan, val), torch.where(bad[:, None], nan, grad), ch.info
+
+
 def mean_response_max_grid() -> int:
     return int(_capi.lib().gp_mean_response_max_grid())
 

@@ -63,7 +63,7 @@
  *      - the L^-1 the prediction READS (gp_predict, gp_predict_ex, gp_predict_z,
  *        gp_predict_solve, gp_predict_cov, gp_fit_predict's Linv) and both buffers of gp_pack_linv /
  *        gp_unpack_linv: 16-byte aligned base, even ldinv, even strideInv (gp_potrf_inv,
- *        gp_trtri, gp_trmv, gp_nll and gp_xval take any L^-1 layout);
+ *        gp_trtri, gp_trmv, gp_nll, gp_xval, gp_alpha and gp_nll_grad take any L^-1 layout);
  *      - every workspace `ws`: 256-byte aligned (gp_dgemm / gp_gemm_ex's split-K scratch and
  *        the `work` vectors of gp_nll / gp_mean_var: 8 bytes);
  *  - stream-ordered and asynchronous on `stream`; no host synchronisation, so calls can be
@@ -715,6 +715,39 @@ int gp_xval(const double* Linv, int ldinv, long long strideInv, int n, const dou
 long long gp_alpha_ws_bytes(int n, int batch);
 int gp_alpha(const double* Linv, int ldinv, long long strideInv, int n, const double* w, int ldw,
              double* alpha, int lda, int batch, void* ws, long long ws_bytes, hipStream_t stream);
+
+/* Analytic gradient of NLL = 1/2 w^T K^-1 w + 1/2 log|K| (the value gp_nll returns) from the L^-1
+ * of gp_potrf_inv: what scipy takes by forward differences of GPmodule's objective in
+ * GPmodule.GP.fit (examples/02...ipynb:80-85: d + 1 further factorisations per gradient, each only
+ * cond(K) eps accurate).  Per problem b, with K = s R + delta I, R_ij = exp(-sum_k beta_k D_ijk^2),
+ * D_ijk = X[i,k] - X[j,k], alpha = K^-1 w and W = K^-1 - alpha alpha^T:
+ *   grad_b[0]     = dNLL/ds      =  1/2 sum_ij W_ij R_ij
+ *   grad_b[1]     = dNLL/ddelta  =  1/2 sum_i  W_ii
+ *   grad_b[2 + k] = dNLL/dbeta_k = -1/2 s sum_ij W_ij R_ij D_ijk^2,   k < d
+ * written at grad + b * ldg (d + 2 values, ldg >= d + 2).
+ *   Linv   the padded L^-1 of gp_potrf_inv under gp_alpha's layout rules: ldinv >= gp_padded_n(n),
+ *          strideInv >= ldinv * gp_padded_n(n), any naturally aligned layout (a 16-B aligned base
+ *          with even ldinv and strideInv selects 16-B loads); column c is taken as zero above
+ *          row c and below row n - 1 whatever the buffer holds there.
+ *   X      the n x d design shared by all problems (row i at X + i * ldx, ldx >= d);
+ *          1 <= d <= GPFIT_MAX_DIM.  beta: d values at beta + b * ldbeta; s: one value per problem.
+ *   alpha  n values at alpha + b * lda, from gp_alpha with the same Linv and w.
+ *   ws     gp_nll_grad_ws_bytes(n, d, batch) bytes, 256-B aligned (the tiles' partial sums; -1
+ *          for a negative size).
+ * No n x n matrix is stored: one workgroup per lower 64 x 64 tile forms its tile of K^-1 = L^-T
+ * L^-1 on fp64 MFMA over k >= the tile's first row (n^3 / 3 flop in all, the factorisation's count
+ * without its dependency chain), subtracts alpha_i alpha_j, recomputes R_ij from X and beta and
+ * writes its d + 2 partial sums; a second launch adds them in ascending tile order.  No atomics:
+ * equal inputs give equal bits, whatever the layout and the problem's position in the batch.
+ * Two launches per 65535 problems.  Stream-ordered, allocates nothing, can be captured into a
+ * hipGraph.  n = 0 or batch = 0: no launch.  A violation returns minus its argument position
+ * before anything is launched.  A problem whose factorisation reported info != 0 has an
+ * unspecified gradient. */
+long long gp_nll_grad_ws_bytes(int n, int d, int batch);
+int gp_nll_grad(const double* Linv, int ldinv, long long strideInv, const double* X, int ldx,
+                int n, int d, const double* beta, int ldbeta, const double* s,
+                const double* alpha, int lda, double* grad, int ldg, int batch, void* ws,
+                long long ws_bytes, hipStream_t stream);
 
 /* Mean-response surfaces of the posterior mean: main effects (nfree = 1) and input pairs
  * (nfree = 2), the GP arithmetic of mean_response.py's compute_mean_response (lines 82-138:
