@@ -19,7 +19,7 @@ TRACE_LIB_PATH = os.path.join(PKG_DIR, "libgpfit_trace.so")
 SOURCES = ["gram.hip", "chol.hip", "predict.hip", "linalg.hip", "profile.hip", "blas.hip",
            "eig.hip", "comm.hip", "rng.hip", "mcmc.hip", "host_rng.hip", "field.hip",
            "summary.hip", "sobol.hip", "xval.hip", "pcatrunc.hip", "response.hip", "jointcov.hip",
-           "nllgrad.hip"]
+           "nllgrad.hip", "sobolx.hip"]
 # Per-file extra flags.  chol.hip: MFMA accumulators in VGPRs (not AGPRs) so the update
 # kernel, whose lookahead block calls the ~250-VGPR diagonal factor, keeps 2 waves/SIMD; and
 # 16-byte LDS reads (ds_read_b128) for the factor's broadcast rows.

@@ -157,6 +157,10 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_ll,
                                  c_void_p]),
+    "gp_sobol_exact_ws_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "gp_sobol_exact": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                               c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll,
+                               c_void_p, c_ll, c_ll, c_ll, c_void_p, c_ll, c_void_p]),
     "gp_predict_cov_ws_bytes": (c_ll, [c_int, c_int, c_int]),
     "gp_predict_cov": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_int, c_void_p, c_int, c_int,
                                c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

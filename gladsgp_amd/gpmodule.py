@@ -189,6 +189,22 @@ class GP:
                                     self._s, self._s, self._y)
         return mean[0].cpu().numpy(), var[0].cpu().numpy()
 
+    def sobol_indices(self, lo=None, hi=None):
+        """(first_order (d,), total_index (d,)): the Sobol' indices of the posterior mean at the
+        fitted theta under inputs uniform on the box ``[lo, hi]`` (default the unit cube), in
+        closed form (gp_sobol_exact, one unit): no design and no sampling error."""
+        from .sensitivity import indices_from_moments
+        d = self._X.shape[1]
+        one = lambda v: torch.full((1,), float(v), dtype=F64, device=self.device)  # noqa: E731
+        box = lambda v: None if v is None else torch.as_tensor(                    # noqa: E731
+            np.broadcast_to(np.asarray(v, dtype=np.float64), (d,)).copy(), device=self.device)
+        if (lo is None) != (hi is None):
+            lo, hi = (0.0 if lo is None else lo), (1.0 if hi is None else hi)
+        E, Q = kernels.sobol_exact(self._X, kernels.alpha(self._chol, self._y), self._beta,
+                                   one(self._s), lo=box(lo), hi=box(hi))
+        _, _, first, total = indices_from_moments(E.reshape(1, 1), Q)
+        return first[0].cpu().numpy(), total[0].cpu().numpy()
+
     def predictor(self, xpred) -> np.ndarray:
         """Posterior mean K(xpred, x) K^-1 y at the fitted theta, shape (m,)."""
         return self._predict(xpred)[0]

@@ -696,6 +696,64 @@ def mean_response(X, alpha, beta, s, effects, t1, t2=None, Xint=None, order: str
     return out
 
 
+def sobol_exact(X, alpha, beta, s, group: int = 1, lo=None, hi=None, out=None):
+    """Closed-form Sobol' ingredients of the posterior means of ``U`` GPs under uniform inputs on
+    the box ``[lo, hi]`` (gp_sobol_exact).  The units are G = U / ``group`` groups of M = ``group``
+    consecutive units.  Returns ``(E, Q)``: ``E`` (U,) the units' means and ``Q`` (G, M, M,
+    2 d + 1) per pair of units of one group ``[tot, main_0 .. main_{d-1}, not_0 .. not_{d-1}]`` =
+    E[f_a f_b], E[E[f_a|x_i] E[f_b|x_i]], E[E[f_a|x_~i] E[f_b|x_~i]] (include/gpfit.h).
+
+    ``X`` (n, d), ``alpha`` (U, n) from :func:`alpha`, ``beta`` (U, d), ``s`` (U,): contiguous
+    float64 device tensors.  ``lo`` / ``hi``: (d,) float64 device tensors with ``hi > lo`` (checked
+    here: one host synchronisation), or both None for the unit box.  ``out``: a pair of contiguous
+    float64 tensors of the results' shapes."""
+    _f64_tensor(X, "X", "(n, d) with 1 <= d", lambda t: t.dim() == 2 and t.shape[1] >= 1)
+    n, d = X.shape
+    _f64_tensor(alpha, "alpha", f"(U, {n})", lambda t: t.dim() == 2 and t.shape[1] == n)
+    U = alpha.shape[0]
+    _f64_tensor(beta, "beta", f"({U}, {d})", lambda t: tuple(t.shape) == (U, d))
+    _f64_tensor(s, "s", f"({U},)", lambda t: tuple(t.shape) == (U,))
+    if d > 32:
+        raise ValueError(f"X: d = {d} exceeds GPFIT_MAX_DIM = 32")
+    if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or group < 1:
+        raise ValueError(f"group: expected an integer >= 1, got {group!r}")
+    M = int(group)
+    if U % M:
+        raise ValueError(f"group: {U} units are no whole number of groups of {M}")
+    G = U // M
+    if (lo is None) != (hi is None):
+        raise ValueError("lo, hi: give both bounds or neither")
+    if lo is not None:
+        _f64_tensor(lo, "lo", f"({d},)", lambda t: tuple(t.shape) == (d,))
+        _f64_tensor(hi, "hi", f"({d},)", lambda t: tuple(t.shape) == (d,))
+    shapes = ((U,), (G, M, M, 2 * d + 1))
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or any(
+                not torch.is_tensor(o) or o.dtype != F64 or tuple(o.shape) != sh or
+                not o.is_contiguous() for o, sh in zip(out, shapes)):
+            raise ValueError(f"out: expected contiguous float64 tensors of shapes {shapes}")
+    ops = [(X, "X"), (alpha, "alpha"), (beta, "beta"), (s, "s")]
+    ops += [(t, nm) for t, nm in ((lo, "lo"), (hi, "hi")) if t is not None]
+    ops += [(o, "out") for o in (out or ())]
+    for t, nm in ops:
+        _check_device(t, nm)
+    if lo is not None and not bool((hi > lo).all()):
+        raise ValueError("lo, hi: every hi must exceed its lo")
+    dev = X.device
+    E, Q = out if out is not None else (torch.empty(sh, dtype=F64, device=dev) for sh in shapes)
+    if U == 0:
+        return E, Q
+    nq = 2 * d + 1
+    nbytes = int(_capi.lib().gp_sobol_exact_ws_bytes(n, d, G, M))
+    ws = _scratch("sobol_exact", dev, nbytes) if nbytes else None
+    _capi.call("gp_sobol_exact", X.data_ptr(), n, d, d, G, M, alpha.data_ptr(), n,
+               beta.data_ptr(), d, s.data_ptr(), lo.data_ptr() if lo is not None else None,
+               hi.data_ptr() if hi is not None else None, E.data_ptr(), 1, Q.data_ptr(), nq,
+               M * nq, M * M * nq, ws.data_ptr() if ws is not None else None,
+               ws.numel() if ws is not None else 0, _stream(dev))
+    return E, Q
+
+
 @dataclass
 class Prepared:
     """Cross-covariance of every test-point chunk, built by :func:`predict_prepare`."""

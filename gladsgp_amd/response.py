@@ -86,6 +86,36 @@ class MeanResponsePrediction(EmulatorPrediction):
         return np.asarray(mean, dtype=np.float64).reshape(self.grid + (-1,))
 
 
+def unit_alpha(model, samples, budget_bytes: int = 2 << 30, group: int | None = None):
+    """``alpha = A^-1 w_hat`` of every (sample, PC) GP of ``samples``, the weights of its posterior
+    mean: per group of GPs under ``budget_bytes`` (at most ``group``) ``kernels.gram`` ->
+    ``cholesky_inverse`` -> ``check`` -> ``kernels.alpha``.  Returns (alpha (S P, n), beta
+    (S P, d), s (S P,), S, P) on the model's device, the units (sample, PC) in sample-major
+    order."""
+    dev = model.device
+    X = model.data.sim_data.t_dev
+    n, d = model.n, model.d
+    beta, s, delta, _ = gp_params(samples, _np(model.LamSim), d, model.P, True)
+    S, P = s.shape
+    U = S * P
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)  # noqa
+    # units (s, j) in s-major order
+    beta_u, s_u, delta_u = t(beta.reshape(U, -1)), t(s.reshape(-1)), t(delta.reshape(-1))
+    w_u = model.w_hat.transpose(0, 1).contiguous().repeat(S, 1)     # (S P, n)
+    npad = kernels.padded_n(n)
+    g = max(1, int(budget_bytes // (8 * (n * n + npad * npad))))
+    if group is not None:
+        g = max(1, min(g, int(group)))
+    alpha = torch.empty((U, n), dtype=F64, device=dev)
+    for a in range(0, U, g):
+        b = min(U, a + g)
+        ch = kernels.cholesky_inverse(kernels.gram(X, beta_u[a:b], s_u[a:b], delta_u[a:b],
+                                                   batch=b - a))
+        ch.check()
+        kernels.alpha(ch, w_u[a:b], out=alpha[a:b])
+    return alpha, beta_u, s_u, S, P
+
+
 def _surfaces(model, samples, effects, nfree, order, targets, ntarget, design, nintegrate,
               round_f32, budget_bytes, group):
     if not isinstance(model, EmulatorModel) or samples is None:
@@ -110,24 +140,9 @@ def _surfaces(model, samples, effects, nfree, order, targets, ntarget, design, n
         # the reference writes its points into a float32 xpred (mean_response.py:122, 195)
         xi = xi.astype(np.float32).astype(np.float64)
         design = None if design is None else design.astype(np.float32).astype(np.float64)
-    beta, s, delta, _ = gp_params(samples, _np(model.LamSim), d, model.P, True)
-    S, P = s.shape
-    U = S * P
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)  # noqa
-    # units (s, j) in s-major order
-    beta_u, s_u, delta_u = t(beta.reshape(U, -1)), t(s.reshape(-1)), t(delta.reshape(-1))
-    w_u = model.w_hat.transpose(0, 1).contiguous().repeat(S, 1)     # (S P, n)
-    npad = kernels.padded_n(n)
-    g = max(1, int(budget_bytes // (8 * (n * n + npad * npad))))
-    if group is not None:
-        g = max(1, min(g, int(group)))
-    alpha = torch.empty((U, n), dtype=F64, device=dev)
-    for a in range(0, U, g):
-        b = min(U, a + g)
-        ch = kernels.cholesky_inverse(kernels.gram(X, beta_u[a:b], s_u[a:b], delta_u[a:b],
-                                                   batch=b - a))
-        ch.check()
-        kernels.alpha(ch, w_u[a:b], out=alpha[a:b])
+    alpha, beta_u, s_u, S, P = unit_alpha(model, samples, budget_bytes, group)
+    U = S * P
     t1 = t(xi)
     effects = np.asarray(effects, dtype=np.int64).reshape((-1, 2) if nfree == 2 else (-1,))
     res =kernels.mean_response(X.contiguous(), alpha, beta_u, s_u, effects, t1,

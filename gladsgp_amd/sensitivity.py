@@ -11,6 +11,12 @@ One documented difference: the reference draws four independent sets of resample
 statistic, and recomputes the same sums in each; here first-order, total and both general indices
 come from ONE common set, so the intervals agree with the reference statistically, not number for
 number.
+
+Beside the estimators stands what they estimate: the function analysed is the emulator's posterior
+mean, a sum of products over the input dimensions under the ARD kernel, so its Sobol' indices
+under uniform inputs have a closed form (``gp_sobol_exact``, ``csrc/sobolx.hip``).
+:func:`exact_indices` returns them with no design, no sampling error and no bootstrap, and, per
+posterior sample, their posterior spread.
 """
 from __future__ import annotations
 
@@ -457,3 +463,130 @@ def emulator_func(model, samples, cast=np.float32, **prediction_kwargs):
         w = pred.w if cast is None else pred.w.astype(cast)
         return np.mean(w, axis=0).astype(np.float64)
     return func
+
+
+# ------------------------------------------------------------------------------------------------
+# the closed form
+# ------------------------------------------------------------------------------------------------
+
+def indices_from_moments(E, Q):
+    """(mean, variance, first_order, total_index) of the mean function of each group from
+    gp_sobol_exact's ``E`` (..., M) and ``Q`` (..., M, M, 2 d + 1): with Eb = mean_a E and
+    Qb = mean_ab Q, V = Qb_tot - Eb^2, S_i = (Qb_main_i - Eb^2) / V, T_i = (Qb_tot - Qb_not_i) / V.
+    numpy arrays or torch tensors."""
+    d = (Q.shape[-1] - 1) // 2
+    Eb = E.mean(-1)
+    Qb = Q.mean(-2).mean(-2)
+    V = Qb[..., 0] - Eb * Eb
+    first = (Qb[..., 1:1 + d] - (Eb * Eb)[..., None]) / V[..., None]
+    total = (Qb[..., :1] - Qb[..., 1 + d:]) / V[..., None]
+    return Eb, V, first, total
+
+
+@dataclass
+class ExactSobolResult:
+    """The exact Sobol' indices of the emulator's posterior mean (:func:`exact_indices`).
+    ``average="mean"``: ``first_order`` / ``total_index`` (P, d), ``mean`` / ``variance`` (P,), the
+    general pair (d,) or None.  ``average="sample"``: the same with a leading axis over the S
+    posterior samples.  Tensors live on the device; :meth:`numpy` gives a host copy."""
+    first_order: object
+    total_index: object
+    general_first_order: object
+    general_total_index: object
+    mean: object
+    variance: object
+    average: str = "mean"
+
+    @property
+    def interaction(self):
+        """total_index - first_order: the share of the variance x_i takes part in through
+        interactions only."""
+        return self.total_index - self.first_order
+
+    def interval(self, confidence_level: float = 0.95) -> dict:
+        """Per statistic name the equal-tailed band over the posterior samples
+        (``average="sample"`` only): the (1 -+ confidence_level) / 2 quantiles along the S axis
+        (numpy's linear rule), as a :class:`ConfidenceInterval`."""
+        if self.average != "sample":
+            raise ValueError("interval: the band is over the posterior samples; use "
+                             "exact_indices(..., average='sample')")
+        return {name: percentile_interval(getattr(self, name), confidence_level)
+                for name in _STAT_NAMES if getattr(self, name) is not None}
+
+    def numpy(self) -> "ExactSobolResult":
+        def h(x):
+            return x.cpu().numpy() if torch.is_tensor(x) else x
+        return ExactSobolResult(h(self.first_order), h(self.total_index),
+                                h(self.general_first_order), h(self.general_total_index),
+                                h(self.mean), h(self.variance), self.average)
+
+
+def exact_indices(model, samples, pcvar=None, average: str = "mean", lo=None, hi=None,
+                  budget_bytes: int = 2 << 30, group: int | None = None) -> ExactSobolResult:
+    """Sobol' indices of the emulator's posterior mean in closed form (gp_sobol_exact): no design,
+    no sampling error, no bootstrap.  The inputs are uniform on the box ``[lo, hi]`` (default the
+    unit cube, where the reference's Saltelli design lives).
+
+    ``average="mean"``: the indices of the driver's ``func`` (sensitivity_indices.py:73-89), the
+    mean over the posterior samples of the predicted PC weights -- the limit of
+    ``PCA_saltelli_sensitivity_indices(emulator_func(model, samples, cast=None), ...)`` as the
+    design grows.  ``average="sample"``: the indices of every posterior sample's own mean
+    function; :meth:`ExactSobolResult.interval` then gives their posterior spread.  ``pcvar``
+    (P,): also the general indices sum_p pcvar_p index_p (utils.py:254-255).
+
+    One difference from the Saltelli path: ``emulator_func`` casts w to float32 per predicted
+    point as the driver does; the closed form has no such cast.
+
+    Per group of GPs under ``budget_bytes`` / ``group`` the alpha chain is
+    :func:`gladsgp_amd.response.unit_alpha`; then one ``kernels.sobol_exact`` per PC."""
+    from . import kernels
+    from .emulator import EmulatorModel
+    from .response import unit_alpha
+    if not isinstance(model, EmulatorModel) or samples is None:
+        raise ValueError("exact_indices needs an EmulatorModel and its samples")
+    if average not in ("mean", "sample"):
+        raise ValueError(f"average: expected 'mean' or 'sample', got {average!r}")
+    dev = model.device
+    d = model.d
+    X = model.data.sim_data.t_dev.contiguous()
+
+    def box(v):
+        if v is None:
+            return None
+        return torch.as_tensor(np.broadcast_to(np.asarray(_host(v), dtype=np.float64),
+                                               (d,)).copy(), dtype=F64, device=dev)
+    if (lo is None) != (hi is None):
+        lo = 0.0 if lo is None else lo
+        hi = 1.0 if hi is None else hi
+    lo, hi = box(lo), box(hi)
+    alpha, beta_u, s_u, S, P = unit_alpha(model, samples, budget_bytes, group)
+    # the S samples of a PC consecutive: unit (j, s)
+    pm = lambda a: a.reshape(S, P, -1).transpose(0, 1).reshape(P * S, -1).contiguous()  # noqa
+    alpha, beta_u, s_u = pm(alpha), pm(beta_u), pm(s_u).reshape(-1)
+    M = S if average == "mean" else 1
+    E = torch.empty(P * S, dtype=F64, device=dev)
+    Q = torch.empty((P * S // M, M, M, 2 * d + 1), dtype=F64, device=dev)
+    gp = S // M                                          # groups per PC
+    for j in range(P):
+        u = slice(j * S, (j + 1) * S)
+        kernels.sobol_exact(X, alpha[u], beta_u[u], s_u[u], group=M, lo=lo, hi=hi,
+                            out=(E[u], Q[j * gp:(j + 1) * gp]))
+    mean, var, first, total = indices_from_moments(E.reshape(P, gp, M), Q.reshape(P, gp, M, M, -1))
+    if average == "mean":
+        mean, var, first, total = mean[:, 0], var[:, 0], first[:, 0], total[:, 0]
+    else:                                                # (P, S, ..) -> (S, P, ..)
+        mean, var = mean.t().contiguous(), var.t().contiguous()
+        first, total = first.transpose(0, 1).contiguous(), total.transpose(0, 1).contiguous()
+    gfirst = gtotal = None
+    if pcvar is not None:
+        pv = torch.as_tensor(np.asarray(_host(pcvar), dtype=np.float64).reshape(-1), dtype=F64,
+                             device=dev)
+        if pv.numel() != P:
+            raise ValueError(f"pcvar: expected {P} values, got {pv.numel()}")
+        gfirst = (pv[:, None] * first).sum(-2)
+        gtotal = (pv[:, None] * total).sum(-2)
+    return ExactSobolResult(first, total, gfirst, gtotal, mean, var, average)
+
+
+def _host(x):
+    return x.cpu().numpy() if torch.is_tensor(x) else x

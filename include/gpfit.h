@@ -793,6 +793,47 @@ int gp_mean_response(const double* X, int n, int d, int ldx, const double* alpha
                      const double* Xint, int I, int ldi,
                      double* out, long long lde, long long ldb, hipStream_t stream);
 
+/* Closed-form Sobol' ingredients of the posterior mean under uniform inputs on the box
+ * prod_k [lo_k, hi_k]: what utils.py:27-256 (saltelli_sensitivity_indices) estimates by sampling
+ * the emulator's mean.  The U = G * M units (one (sample, PC) GP each: alpha of gp_alpha, beta,
+ * s) are G groups of M consecutive units, unit u = g * M + a.  With w_k = hi_k - lo_k and
+ *   I_k(u,n)       = (1/w_k) int exp(-beta_uk (x - X[n,k])^2) dx
+ *   J_k(u,n;v,n')  = (1/w_k) int exp(-beta_uk (x - X[n,k])^2 - beta_vk (x - X[n',k])^2) dx
+ * (finite sums of erf and exp) the call returns
+ *   E[u*incE]                         = s_u sum_n alpha_un prod_k I_k(u,n)          (the mean)
+ *   Q[g*ldqg + a*ldqa + b*ldq + 0]     = s_u s_v sum_nn' alpha_un alpha_vn' prod_k J_k
+ *   Q[.. + 1 + i]                     = s_u s_v sum_nn' alpha_un alpha_vn' J_i
+ *                                       prod_{k != i} I_k(u,n) I_k(v,n')
+ *   Q[.. + 1 + d + i]                 = s_u s_v sum_nn' alpha_un alpha_vn' I_i(u,n) I_i(v,n')
+ *                                       prod_{k != i} J_k
+ * for every pair u = g M + a, v = g M + b of one group (pairs across groups are not computed):
+ * E[f_u f_v], E[E[f_u|x_i] E[f_v|x_i]] and E[E[f_u|x_~i] E[f_v|x_~i]].  For the mean function of
+ * a group, f = (1/M) sum_a f_a, with Eb = mean_a E and Qb = mean_ab Q: V = Qb_tot - Eb^2,
+ * S_i = (Qb_main_i - Eb^2) / V, T_i = (Qb_tot - Qb_not_i) / V.
+ *   X        row-major n x d, ldx >= d;  alpha: n values at alpha + u * lda;  beta: d values at
+ *            beta + u * ldbeta;  s: one value per unit.  1 <= d <= GPFIT_MAX_DIM, M >= 1.
+ *   lo, hi   d device values each, or both NULL for the unit box.  hi_k <= lo_k cannot be seen
+ *            from the host: the result is then unspecified.
+ *   Q        ldq >= 2 d + 1, ldqa >= (M - 1) ldq + 2 d + 1, ldqg >= (M - 1) (ldqa + ldq) +
+ *            2 d + 1; both triangles are written, with the same bits; nothing else is.
+ *   ws       gp_sobol_exact_ws_bytes(n, d, G, M) bytes, 256-B aligned (0 when n = 0 or G = 0;
+ *            -1 for a negative size).
+ * fp64 throughout, no atomics, every summation order fixed by (n, d) alone: equal inputs give
+ * equal bits whatever G, M, the unit's position and the strides; a pair is computed once, as
+ * (a, b) with a <= b, and mirrored; the (a, a) entry of a grouped call is the M = 1 call's.  The leave-one-out products
+ * are prefix / suffix products, never quotients, so an underflowed J_i leaves Q_not_i finite.
+ * The error of a value is a small multiple of eps times the same sum with |alpha_un alpha_vn'|
+ * (DESIGN.md 4.6h).  Stream-ordered, allocates nothing, can be captured into a hipGraph.
+ * n = 0: E and Q are written as 0.  G = 0: validated, nothing launched, nothing written.  A
+ * violation returns minus its argument position (1 = X ... 21 = ws_bytes) before any launch;
+ * lo without hi -13, hi without lo -12. */
+long long gp_sobol_exact_ws_bytes(int n, int d, int G, int M);
+int gp_sobol_exact(const double* X, int n, int d, int ldx, int G, int M, const double* alpha,
+                   int lda, const double* beta, int ldbeta, const double* s, const double* lo,
+                   const double* hi, double* E, long long incE, double* Q, long long ldq,
+                   long long ldqa, long long ldqg, void* ws, long long ws_bytes,
+                   hipStream_t stream);
+
 /* Joint predictive covariance of the m test points of a call, per problem b, from the L^-1 of
  * gp_potrf_inv: what SepiaEmulatorPrediction forms for every (sample, PC) GP before it draws the
  * PC weights jointly.  With V_b = Linv_b K*_b (n x m; K* the cross-covariance gp_predict uses):
